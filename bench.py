@@ -2,9 +2,21 @@
 """Headline benchmark: MPM substeps/s on the synthetic 'sheet-500k' scene (497,762 particles, 256^3 grid;
 BASELINE.json metric) on N MI355X GPUs of one node.
 
-    python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and nothing else: it builds the scene and the solver, runs W warm-up substeps, times
+ONE window of exactly K substeps (synchronize on both sides), writes the outputs when --dump-outputs is given and prints the result
+line: `value` = K / the window's time, `ms_per_step` = the window's time / K in milliseconds.  Everything else the benchmark can
+measure is behind --full (below).  --dump-outputs DIR writes what a caller of the substep loop receives after the last timed substep:
+particle_x, the one array both reference drivers read back after their calls of p2g2p (the positions of every particle, global particle
+order), as DIR/particle_x.npy in float32; beyond 60 MB the array keeps a fixed, seeded sample of its rows.  The scenes are seeded: the
+same arguments give the same inputs in every run.  The outputs of two runs agree to a few units in the last place of the coordinates
+over a few hundred substeps (headline scene, 220 substeps: 3.6e-7 m at most, 0.1 % of the coordinates differ at all; 2020 substeps, the
+sheet draping over the sphere: 1.5e-4 m), not bit for bit: p2g flushes its node tiles into the grid with fp32 atomics, whose order the hardware does
+not fix, and the cloth amplifies that rounding noise with time.  The solver's internal fields (C, stress, vertex_force, ...) are not
+written: on the headline scene at t = 0 they consist of such noise (stress of a sheet in free fall: 1e-11) and compare to nothing.
 
 A "step" is one substep (MPMWARP.p2g2p: stress -> p2g -> grid -> g2p) over the whole scene, inputs resident in
 HBM before the timed region.  N > 1 shards particles by spatial slab (strong scaling: total work fixed) with an
@@ -13,7 +25,8 @@ RCCL halo exchange of the shared grid blocks after p2g (mpmavatar_amd/dist.py).
 With --gpus N > 1 and no launcher in the environment (WORLD_SIZE unset) the script starts the N ranks itself
 (torch.distributed.run, 127.0.0.1); on a box with fewer GPUs it stops with a message instead.
 
-Rank 0 prints ONE JSON line.  Besides the contract keys it carries
+Rank 0 prints ONE JSON line.  With --full the headline is the mean over windows of K substeps that cover at least 600 substeps (see the
+comment at RESORT_SPAN), and besides the contract keys the line carries
   "roofline":     dominant kernel OF THE TIMED LOOP (HIP events around the fused launches, same kernels as the timed
                   region), algorithmic bytes per launch / launch time vs 8 TB/s
   "kernels":      every launch of the timed loop the same way ("kernels_mode": "fused-loop"), and
@@ -153,6 +166,27 @@ def cpu_baseline(sc, budget_s=15.0, serial_budget_s=8.0):
     return res
 
 
+DUMP_FIELDS = ("particle_x",)   # what the caller of the substep loop reads back (see the module docstring)
+DUMP_CAP_BYTES = 60 * 1000 * 1000
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: float32 array} -> path/<name>.npy.  Over DUMP_CAP_BYTES in all, every array with more than 1024 rows keeps
+    a seeded sample of its rows (sorted indices drawn by default_rng(crc32 of the array's name): the same rows in every run of the same
+    scene)."""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, DUMP_CAP_BYTES / max(total, 1))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if frac < 1.0 and a.shape[0] > 1024:
+            rows = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.shape[0], size=int(a.shape[0] * frac), replace=False))
+            a = a[rows]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     # stdout carries exactly one line (the JSON result); everything else this process prints -- the shim repeats the
     # reference's "Particles initialized from torch data." messages -- goes to stderr
@@ -174,11 +208,15 @@ def _main(out_stream):
     ap.add_argument("--scene", default="sheet-500k")
     ap.add_argument("--mode", default="fast", choices=["fast", "baseline"])
     ap.add_argument("--rebin-interval", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernels", action="store_true", help="skip the HIP-event passes")
-    ap.add_argument("--windows", type=int, default=0, help="timed windows of --steps substeps each (median reported); "
-                    "0 = 7 when --steps < 100, else 1")
-    ap.add_argument("--advance", type=int, default=2000, help="untimed substeps before the second (draped-state) measurement; "
+    ap.add_argument("--full", action="store_true", help="also measure everything behind the headline figure: windows covering >= 600 substeps, "
+                    "copy bandwidth, per-kernel stamps and roofline, the reference's phases, draped state, CPU baseline; N > 1: shard floor, "
+                    "weak scaling (the --no-* / --advance options below choose among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write particle_x after the last timed substep as DIR/particle_x.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-kernels", action="store_true", help="--full: skip the HIP-event passes")
+    ap.add_argument("--windows", type=int, default=0, help="timed windows of --steps substeps each (mean reported); 0 = one window, "
+                    "with --full as many as cover 600 substeps (at least 7 when --steps < 100)")
+    ap.add_argument("--advance", type=int, default=2000, help="--full: untimed substeps before the second (draped-state) measurement; "
                     "0 = skip it")
     ap.add_argument("--pre-advance", type=int, default=0, help="diagnostics: untimed substeps BEFORE the warm-up (profile the "
                     "draped state with --advance 0)")
@@ -286,8 +324,8 @@ def _main(out_stream):
         return float(el.item())
 
     mark("scene + solver built")
-    copy_bw = measure_copy_bandwidth(dev) if rank == 0 else None
-    mark("copy bandwidth measured")
+    copy_bw = measure_copy_bandwidth(dev) if rank == 0 and args.full else None
+    mark("copy bandwidth measured" if args.full else "copy bandwidth skipped (--full measures it)")
     if args.pre_advance > 0:
         run(args.pre_advance)
     run(args.warmup)
@@ -298,9 +336,9 @@ def _main(out_stream):
     # RESORT_SPAN substeps -- more than two re-sort intervals of the scene at t = 0 (one every ~250 substeps; every 65-100 once draped) --
     # and `value` is the MEAN rate over all of them: K x windows / total bracketed time, with the re-sorts that fell into the windows
     # paid for in it (round 5 reported the median window, which by construction never contained one).  The median
-    # window, the fastest and the slowest stay beside it.
+    # window, the fastest and the slowest stay beside it.  That is the --full measurement; a plain run times one window of exactly K.
     RESORT_SPAN = 600
-    n_win = args.windows if args.windows > 0 else max(7 if args.steps < 100 else 1, -(-RESORT_SPAN // args.steps))
+    n_win = args.windows if args.windows > 0 else (max(7 if args.steps < 100 else 1, -(-RESORT_SPAN // args.steps)) if args.full else 1)
     rebins0 = sim.solver.stats()["rebins"] if not sharded else None
     win_raw = [timed(args.steps) for _ in range(n_win)]
     rebins_timed = (sim.solver.stats()["rebins"] - rebins0) if not sharded else None
@@ -325,11 +363,22 @@ def _main(out_stream):
     if copy_bw:
         out["copy_bandwidth"] = copy_bw
     mark("headline windows timed")
+    if args.dump_outputs:
+        # what the timed loop computed in its last substep, read back the way a caller does (before --full advances the state further)
+        if sharded:
+            glob_state = mdist.gather_global_state(box["ss"])          # collective; global particle order
+            arrays = {f: glob_state[f] for f in DUMP_FIELDS if f in glob_state}
+        else:
+            arrays = {f: getattr(sim.state, f).detach().cpu().numpy() for f in DUMP_FIELDS}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, arrays)
+        out["outputs"] = {"dir": args.dump_outputs, "after_substep": int(args.pre_advance + args.warmup + n_win * args.steps), "arrays": sorted(arrays)}
+        mark("outputs written")
     # N > 1: everything below this point is extra information around a headline value that is already measured.  It involves more
     # collectives, a second sharded scene and thousands of further substeps on hardware this code has never run on: if it is not through
     # within --extras-budget seconds, rank 0 prints the line as far as it got and all ranks leave (same timer on every rank).
     extras_timer = None
-    if world > 1 and args.extras_budget > 0:
+    if world > 1 and args.full and args.extras_budget > 0:
         import threading
 
         def _bail():
@@ -354,7 +403,7 @@ def _main(out_stream):
                               "fallback_particles": st["n_fallback_particles"], "alg_bytes_per_substep": b_alg["substep"]})
         out["substep_GBps"] = b_alg["substep"] / (ms_per_step * 1e-3) / 1e9
         out["substep_frac_of_hbm_peak"] = out["substep_GBps"] / HBM_PEAK_GBS
-        if not args.no_kernels and args.mode == "fast":
+        if args.full and not args.no_kernels and args.mode == "fast":
             # (1) the launches of the timed loop itself: HIP events on the solver's stream around each fused launch
             pb = phase_bytes(sc, n_act, n_col, n_mov)
             cloth = sc.n_elements > 0
@@ -436,7 +485,7 @@ def _main(out_stream):
                     k["frac"] = k["GBps"] / HBM_PEAK_GBS
                 phases.append(k)
             out["phases"], out["phases_mode"] = phases, "per-phase (un-fused launches, one sync each; not the timed loop)"
-    if sharded and not args.no_kernels:
+    if sharded and args.full and not args.no_kernels:
         # per-rank view of rank 0: its launches of the sharded loop (HIP events, same kernels as the timed region), the
         # dominant one against the roofline with this rank's algorithmic bytes, and what the halo exchange moves
         ss = box["ss"]
@@ -490,7 +539,7 @@ def _main(out_stream):
                            "re_partitions": box["ss"].migrations, "on_device_migrations": box["ss"].trad_migrations,
                            "particles_migrated_on_device": box["ss"].trad_migrated}
     mark("kernel events")
-    if sharded and world > 1 and not args.no_shard_floor:
+    if sharded and world > 1 and args.full and not args.no_shard_floor:
         # What this N can reach at best: rank 0 runs ITS shard (owned particles + ghost copies) as an ordinary single-GPU scene, no
         # exchange at all -- the per-rank compute floor of the slab decomposition (three latency-floored launches per substep).
         # The first run on a real node is then self-explaining: measured value vs this bound = what the halo exchange costs.
@@ -517,7 +566,7 @@ def _main(out_stream):
         finally:
             barrier()               # (every rank, whatever happened on rank 0: the others wait here)
     mark("shard floor")
-    if sharded and world > 1 and not weak_only and not args.no_weak and (args.scene == "sheet-500k" or args.weak_n):
+    if sharded and world > 1 and args.full and not weak_only and not args.no_weak and (args.scene == "sheet-500k" or args.weak_n):
         # the regime the slab decomposition is made for: the same per-rank work at every N (one sheet's worth of particles per
         # rank: N stacked copies of the headline sheet in the same grid).  Reported beside the strong-scaling headline value.
         try:
@@ -540,7 +589,7 @@ def _main(out_stream):
         except Exception as e:  # noqa: BLE001 - the headline line must come out whatever happens here
             out["weak_scaling"] = {"error": f"{type(e).__name__}: {e}"}
     mark("weak scaling")
-    if args.advance > 0:
+    if args.full and args.advance > 0:
         # the steady state: after `advance` more substeps the sheet lies draped over the sphere, moves at metres per second and
         # the particle order is rebuilt every few dozen substeps; re-sorts inside the window are part of the number
         run(args.advance)
@@ -558,7 +607,7 @@ def _main(out_stream):
                                   "fallback_particles": st["n_fallback_particles"],
                                   "substep_frac_of_hbm_peak": b_d["substep"] / (out["ms_per_step_draped"] * 1e-3) / 1e9 / HBM_PEAK_GBS})
     mark("draped state")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(sc)
         mark("cpu baseline")
     if extras_timer is not None:

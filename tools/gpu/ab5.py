@@ -20,7 +20,7 @@ for sc in a.scenes.split(","):
                 env["MPMHIP_LIB"] = os.path.join(ROOT, "mpmavatar_amd", "lib", "variants", f"libmpmhip_{name}.so")
             for kv in filter(None, envs.split(";")):
                 k, _, v = kv.partition("="); env[k] = v
-            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--scene", sc, "--steps", str(a.steps), "--warmup", "40", "--no-cpu-baseline",
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--scene", sc, "--steps", str(a.steps), "--warmup", "40", "--full", "--no-cpu-baseline",
                    "--advance", str(a.advance), "--pre-advance", str(a.pre_advance)]
             r = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT)
             line = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -7,7 +7,7 @@
 # outputs under gpurun_out/prof_<tag>_<scene>/ ; tools/summarize_prof.py condenses them into profiles/
 SC=$1; TAG=$2; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_${TAG}_${SC}; mkdir -p $O; cd $R
 CPU="--no-cpu-baseline"; [ "$SC" = "sheet-500k" ] && CPU=""
-python bench.py --scene $SC --steps 400 --warmup 40 $CPU > $O/bench_fast.json 2> $O/bench_fast.err
+python bench.py --full --scene $SC --steps 400 --warmup 40 $CPU > $O/bench_fast.json 2> $O/bench_fast.err
 tail -c 600 $O/bench_fast.json; echo
 cd /tmp && export TMPDIR=/tmp
 ARGS="--scene $SC --steps 200 --warmup 40 --no-cpu-baseline --no-kernels --advance 0"

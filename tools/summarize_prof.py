@@ -69,7 +69,7 @@ for scene in scenes:
         if line:
             o = json.loads(line[-1])
             json.dump(o, open(f"profiles/{tag}_{scene}_bench.json", "w"), indent=1)
-            out.append(f"\n# bench.py --scene {scene} --steps 400 --warmup 40\n")
+            out.append(f"\n# bench.py --full --scene {scene} --steps 400 --warmup 40\n")
             out.append(f"value {o['value']:.0f} substeps/s ({o['ms_per_step']*1e3:.1f} us/substep), whole-substep fraction of 8 TB/s (algorithmic bytes) "
                        f"{o.get('substep_frac_of_hbm_peak', float('nan')):.3f}; after {o.get('draped', {}).get('advance', 0)} more substeps: "
                        f"{o.get('value_draped', float('nan')):.0f} substeps/s, {o.get('draped', {}).get('rebins_in_window')} re-sorts in the window\n")
