@@ -28,6 +28,29 @@ __global__ void k_mesh_store(float *pts, float *vel, const float *x, const float
 }
 
 bool fast_mode(const mpmhip_ctx *c) { return c->cfg.mode == MPMHIP_MODE_FAST; }
+
+// the multi-GPU entry points exist in the fast mode only (`also`: whatever else the entry point needs under the same message)
+int dist_only(mpmhip_ctx *c, bool also = true) {
+  return (fast_mode(c) && also) ? MPMHIP_OK : fail(c, MPMHIP_ERR_INVALID, "dist: only the fast mode shards across GPUs");
+}
+
+// Preconditions of every stepping entry point.  The back ends read the body mesh through cur_pts + cur_f * cur_vel
+// (device-to-device; the reference's .cpu().numpy() round trip per substep, mpm_solver.py:282-302, is not reproduced).
+int step_prepare(mpmhip_ctx *c, const float *mesh_x, const float *mesh_v, float mesh_f, int n_joint_t = 0) {
+  if (!c->st_bound || !c->md_bound) return fail(c, MPMHIP_ERR_STATE, "step: state/model not bound");
+  if (n_joint_t < 0 || n_joint_t > c->n_trad) return fail(c, MPMHIP_ERR_INVALID, "step: n_joint_t out of range");
+  if ((mesh_x || mesh_v) && !c->mesh_points) return fail(c, MPMHIP_ERR_STATE, "step: mesh_x/mesh_v given but no body mesh");
+  c->cur_pts = mesh_x ? mesh_x : c->mesh_points;
+  c->cur_vel = mesh_v ? mesh_v : c->mesh_vel;
+  c->cur_f = (mesh_x && mesh_v) ? mesh_f : 0.0f;
+  return MPMHIP_OK;
+}
+
+// keep the context's copy of the body mesh (the reference's wp.Mesh) current
+void mesh_store(mpmhip_ctx *c, const float *mesh_x, const float *mesh_v) {
+  size_t nm = (size_t)c->num_mesh_v * 3;
+  hipLaunchKernelGGL(k_mesh_store, (unsigned)((nm + 255) / 256), 256, 0, c->stream, c->mesh_points, c->mesh_vel, mesh_x, mesh_v, c->cur_f, nm);
+}
 }  // namespace
 
 extern "C" {
@@ -348,21 +371,12 @@ int mpmhip_add_velocity_rotation(mpmhip_ctx *c, const float point[3], const floa
 }
 
 static int step_checked(mpmhip_ctx *c, const StepArgs &a) {
-  if (!c->st_bound || !c->md_bound) return fail(c, MPMHIP_ERR_STATE, "step: state/model not bound");
-  if (a.n_joint_t < 0 || a.n_joint_t > c->n_trad) return fail(c, MPMHIP_ERR_INVALID, "step: n_joint_t out of range");
-  if ((a.mesh_x || a.mesh_v) && !c->mesh_points) return fail(c, MPMHIP_ERR_STATE, "step: mesh_x/mesh_v given but no body mesh");
-  // the backends read the body mesh through cur_pts + cur_f * cur_vel (device-to-device; the reference's
-  // .cpu().numpy() round trip per substep, mpm_solver.py:282-302, is not reproduced)
-  c->cur_pts = a.mesh_x ? a.mesh_x : c->mesh_points;
-  c->cur_vel = a.mesh_v ? a.mesh_v : c->mesh_vel;
-  c->cur_f = (a.mesh_x && a.mesh_v) ? a.mesh_f : 0.0f;
-  int rc = fast_mode(c) ? fast_step(c, a) : baseline_step(c, a);
+  int rc = step_prepare(c, a.mesh_x, a.mesh_v, a.mesh_f, a.n_joint_t);
   if (rc) return rc;
+  if ((rc = fast_mode(c) ? fast_step(c, a) : baseline_step(c, a))) return rc;
   if (a.mesh_store && (a.mesh_x || a.mesh_v)) {
     ScopedPhase ph(c, "update_mesh_positions");
-    size_t nm = (size_t)c->num_mesh_v * 3;
-    hipLaunchKernelGGL(k_mesh_store, (unsigned)((nm + 255) / 256), 256, 0, c->stream, c->mesh_points, c->mesh_vel,
-                       a.mesh_x, a.mesh_v, c->cur_f, nm);
+    mesh_store(c, a.mesh_x, a.mesh_v);
   }
   c->time = c->time + c->time_inc(a.dt);  // mpm_solver.py:536
   c->substeps += 1;
@@ -398,88 +412,71 @@ int mpmhip_steps(mpmhip_ctx *c, float dt, int32_t n, const float *mesh_x, const 
   return MPMHIP_OK;
 }
 
-extern "C++" {
-namespace mpm {
-void mesh_store_launch(mpmhip_ctx *c, const StepArgs &a) {
-  size_t nm = (size_t)c->num_mesh_v * 3;
-  hipLaunchKernelGGL(k_mesh_store, (unsigned)((nm + 255) / 256), 256, 0, c->stream, c->mesh_points, c->mesh_vel, a.mesh_x, a.mesh_v, c->cur_f, nm);
-}
-}  // namespace mpm
-}  // extern "C++"
-
 int mpmhip_dist_enable(mpmhip_ctx *c) {
   CHECK_CTX(c);
-  if (!fast_mode(c)) return fail(c, MPMHIP_ERR_INVALID, "dist: only the fast mode shards across GPUs");
+  if (int rc = dist_only(c)) return rc;
   return fast_dist_enable(c);
 }
 int mpmhip_dist_set_ghost_mode(mpmhip_ctx *c, int32_t ghosts_gather) {
   CHECK_CTX(c);
-  if (!fast_mode(c)) return fail(c, MPMHIP_ERR_INVALID, "dist: only the fast mode shards across GPUs");
+  if (int rc = dist_only(c)) return rc;
   return fast_dist_set_ghost_mode(c, ghosts_gather);
 }
 int mpmhip_dist_set_mass_span(mpmhip_ctx *c, float min_mass, float max_mass) {
   CHECK_CTX(c);
-  if (!fast_mode(c)) return fail(c, MPMHIP_ERR_INVALID, "dist: only the fast mode shards across GPUs");
+  if (int rc = dist_only(c)) return rc;
   if (min_mass > 0.0f && !(max_mass >= min_mass)) return fail(c, MPMHIP_ERR_INVALID, "dist_set_mass_span: max_mass < min_mass");
   return fast_dist_set_mass_span(c, min_mass, max_mass);
 }
 int mpmhip_dist_ghost_pack(mpmhip_ctx *c) {
   CHECK_CTX(c);
-  if (!fast_mode(c)) return fail(c, MPMHIP_ERR_INVALID, "dist: only the fast mode shards across GPUs");
+  if (int rc = dist_only(c)) return rc;
   return fast_dist_ghosts(c, 1);
 }
 int mpmhip_dist_ghost_unpack(mpmhip_ctx *c) {
   CHECK_CTX(c);
-  if (!fast_mode(c)) return fail(c, MPMHIP_ERR_INVALID, "dist: only the fast mode shards across GPUs");
+  if (int rc = dist_only(c)) return rc;
   return fast_dist_ghosts(c, 0);
 }
 int mpmhip_dist_num_blocks(const mpmhip_ctx *c) { return (c && c->fast) ? fast_dist_num_blocks(c) : 0; }
 int mpmhip_dist_drift_flag(mpmhip_ctx *c, int32_t *flag) {
   CHECK_CTX(c);
-  if (!fast_mode(c)) return fail(c, MPMHIP_ERR_INVALID, "dist: only the fast mode shards across GPUs");
+  if (int rc = dist_only(c)) return rc;
   if (!flag) return fail(c, MPMHIP_ERR_INVALID, "dist_drift_flag: null output");
   return fast_dist_drift_flag(c, flag);
 }
 int mpmhip_dist_rebin(mpmhip_ctx *c, uint8_t *active_map) {
   CHECK_CTX(c);
-  if (!fast_mode(c)) return fail(c, MPMHIP_ERR_INVALID, "dist: only the fast mode shards across GPUs");
+  if (int rc = dist_only(c)) return rc;
   return fast_dist_rebin(c, active_map);
 }
 int mpmhip_dist_set_peers(mpmhip_ctx *c, int32_t n_peers, const mpmhip_dist_peer *peers) {
   CHECK_CTX(c);
-  if (!fast_mode(c)) return fail(c, MPMHIP_ERR_INVALID, "dist: only the fast mode shards across GPUs");
+  if (int rc = dist_only(c)) return rc;
   return fast_dist_set_peers(c, n_peers, peers);
 }
 int mpmhip_dist_step_begin(mpmhip_ctx *c, float dt, const float *mesh_x, const float *mesh_v, float mesh_advect,
                            const float *joint_traditional_v, int32_t n_joint_t, const float *joint_verts_v,
                            const float *joint_faces_v) {
   CHECK_CTX(c);
-  if (!fast_mode(c)) return fail(c, MPMHIP_ERR_INVALID, "dist: only the fast mode shards across GPUs");
-  if (!c->st_bound || !c->md_bound) return fail(c, MPMHIP_ERR_STATE, "step: state/model not bound");
-  if ((mesh_x || mesh_v) && !c->mesh_points) return fail(c, MPMHIP_ERR_STATE, "step: mesh_x/mesh_v given but no body mesh");
+  if (int rc = dist_only(c)) return rc;
+  if (int rc = step_prepare(c, mesh_x, mesh_v, mesh_advect)) return rc;
   StepArgs a{dt, mesh_x, mesh_v, mesh_advect, true, joint_traditional_v, joint_traditional_v ? n_joint_t : 0, joint_verts_v, joint_faces_v};
-  c->cur_pts = a.mesh_x ? a.mesh_x : c->mesh_points;
-  c->cur_vel = a.mesh_v ? a.mesh_v : c->mesh_vel;
-  c->cur_f = (a.mesh_x && a.mesh_v) ? a.mesh_f : 0.0f;
   c->fast_dt = dt;
   int rc = fast_dist_phase(c, 0, a);
   if (rc) return rc;
-  if (a.mesh_x || a.mesh_v) {  // keep the context's wp.Mesh copy current (used by the next collective re-sort)
-    size_t nm = (size_t)c->num_mesh_v * 3;
-    hipLaunchKernelGGL(k_mesh_store, (unsigned)((nm + 255) / 256), 256, 0, c->stream, c->mesh_points, c->mesh_vel,
-                       a.mesh_x, a.mesh_v, c->cur_f, nm);
-  }
+  if (mesh_x || mesh_v) mesh_store(c, mesh_x, mesh_v);  // (the copy is what the next collective re-sort bins the faces from)
   return MPMHIP_OK;
 }
 int mpmhip_dist_step_mid(mpmhip_ctx *c) {
   CHECK_CTX(c);
-  if (!fast_mode(c) || !c->fast) return fail(c, MPMHIP_ERR_INVALID, "dist: only the fast mode shards across GPUs");
+  if (int rc = dist_only(c, c->fast)) return rc;
   StepArgs a{};
   return fast_dist_phase(c, 1, a);
 }
 int mpmhip_dist_step_end(mpmhip_ctx *c) {
   CHECK_CTX(c);
-  if (!fast_mode(c) || !c->fast) return fail(c, MPMHIP_ERR_INVALID, "dist: only the fast mode shards across GPUs");
+  if (int rc = dist_only(c, c->fast)) return rc;
   StepArgs a{};
   int rc = fast_dist_phase(c, 2, a);
   if (rc) return rc;
@@ -502,25 +499,20 @@ int mpmhip_rccl_set_ghosts(mpmhip_ctx *c, int32_t n_peers, const int32_t *peer_r
                            const int32_t *n_send_e, const int32_t *const *send_e, const int32_t *n_recv_e,
                            const int32_t *const *recv_e) {
   CHECK_CTX(c);
-  if (!fast_mode(c)) return fail(c, MPMHIP_ERR_INVALID, "dist: only the fast mode shards across GPUs");
+  if (int rc = dist_only(c)) return rc;
   return fast_rccl_set_ghosts(c, n_peers, peer_ranks, n_send_p, send_p, n_recv_p, recv_p, n_send_e, send_e, n_recv_e, recv_e);
 }
 int mpmhip_rccl_steps(mpmhip_ctx *c, float dt, int32_t n, int64_t step_index, int32_t rebin_interval, const float *mesh_x,
                       const float *mesh_v, const float *joint_traditional_v, int32_t n_joint_t, const float *joint_verts_v,
                       const float *joint_faces_v) {
   CHECK_CTX(c);
-  if (!fast_mode(c)) return fail(c, MPMHIP_ERR_INVALID, "dist: only the fast mode shards across GPUs");
-  if (!c->st_bound || !c->md_bound) return fail(c, MPMHIP_ERR_STATE, "step: state/model not bound");
-  if ((mesh_x || mesh_v) && !c->mesh_points) return fail(c, MPMHIP_ERR_STATE, "step: mesh_x/mesh_v given but no body mesh");
+  if (int rc = dist_only(c)) return rc;
+  if (int rc = step_prepare(c, mesh_x, mesh_v, 0.0f)) return rc;  // (fast_rccl_steps sets the advection factor per substep)
   c->fast_dt = dt;
   int rc = fast_rccl_steps(c, dt, n, step_index, rebin_interval, mesh_x, mesh_v, joint_traditional_v,
                            joint_traditional_v ? n_joint_t : 0, joint_verts_v, joint_faces_v);
   if (rc) return rc;
-  if (n > 0 && (mesh_x || mesh_v)) {
-    size_t nm = (size_t)c->num_mesh_v * 3;
-    hipLaunchKernelGGL(k_mesh_store, (unsigned)((nm + 255) / 256), 256, 0, c->stream, c->mesh_points, c->mesh_vel, mesh_x,
-                       mesh_v, c->cur_f, nm);
-  }
+  if (n > 0 && (mesh_x || mesh_v)) mesh_store(c, mesh_x, mesh_v);
   return MPMHIP_OK;
 }
 
@@ -561,14 +553,14 @@ int mpmhip_set_debug_flags(mpmhip_ctx *c, int32_t flags) {
 
 int mpmhip_dist_halo_bytes(mpmhip_ctx *c, int64_t *out) {
   CHECK_CTX(c);
-  if (!fast_mode(c) || !c->fast || !out) return fail(c, MPMHIP_ERR_INVALID, "dist: only the fast mode shards across GPUs");
+  if (int rc = dist_only(c, c->fast && out)) return rc;
   *out = fast_dist_halo_bytes(c);
   return MPMHIP_OK;
 }
 
 int mpmhip_dist_halo_transport(mpmhip_ctx *c, int32_t *out) {
   CHECK_CTX(c);
-  if (!fast_mode(c) || !c->fast || !out) return fail(c, MPMHIP_ERR_INVALID, "dist: only the fast mode shards across GPUs");
+  if (int rc = dist_only(c, c->fast && out)) return rc;
   *out = fast_dist_halo_transport(c);
   return MPMHIP_OK;
 }

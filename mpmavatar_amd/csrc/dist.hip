@@ -26,10 +26,10 @@ __global__ void k_link_ping(unsigned *data, int n, int *cnt, int *flag, int seq)
 }
 
 __global__ void k_link_check(const unsigned *data, int n, const int *flag, int seq, int *counters) {
-  link_wait(flag, seq, counters + 10, LINK_HANDSHAKE_TICKS);
+  link_wait(flag, seq, counters + CNT_LINK_TIMEOUT, LINK_HANDSHAKE_TICKS);
   int bad = 0;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) bad += data[i] != link_pattern(seq, i);
-  if (bad) atomicAdd(counters + 11, bad);
+  if (bad) atomicAdd(counters + CNT_LINK_BAD, bad);
 }
 
 
@@ -40,7 +40,7 @@ __global__ void k_post_flag(const int *value, int *host_sig, int seq) {
   __hip_atomic_store(host_sig + SIG_DSEQ, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-__global__ void k_link_verdict(int *counters) { counters[12] = (counters[10] != 0 || counters[11] != 0) ? 1 : 0; }
+__global__ void k_link_verdict(int *counters) { counters[CNT_LINK_VOTE] = (counters[CNT_LINK_TIMEOUT] != 0 || counters[CNT_LINK_BAD] != 0) ? 1 : 0; }
 
 
 __global__ void k_halo_pack(HaloTab tb, GridPtrs g) { halo_pack_wg<false>(tb, g, (int)blockIdx.x); }
@@ -50,7 +50,7 @@ __global__ void k_halo_add(HaloTab tb, GridPtrs g) {
   int p = tab_peer(tb, blockIdx.x);
   int t = ((int)blockIdx.x - tb.wg_off[p]) * blockDim.x + threadIdx.x;
   int CH = tb.with_mov ? 8 : 4;
-  if (tb.sig[p]) link_wait(tb.sig[p], tb.seq, g.counters + 10);
+  if (tb.sig[p]) link_wait(tb.sig[p], tb.seq, g.counters + CNT_LINK_TIMEOUT);
   if (t >= tb.n_blocks[p] * CH * 64) return;
   int l = t & 63, ch = (t >> 6) % CH, i = t / (CH * 64);
   int blk = tb.blocks[p][i];
@@ -444,13 +444,13 @@ static int rccl_link_setup(mpmhip_ctx *c) {
   const char *fault = getenv("MPMHIP_LINK_FAULT");  // tests: this rank pretends its links failed
   if (fault && *fault && atoi(fault) == r.rank) bad = 1;
   // agree before the handshake: a rank without its links would leave its neighbours waiting for pings
-  int *vote = f->g.counters + 12;
+  int *vote = f->g.counters + CNT_LINK_VOTE, *vote_all = f->g.counters + CNT_LINK_VOTE_ALL;
   MPM_HIP_CHECK(c, hipMemcpyAsync(vote, &bad, sizeof(int), hipMemcpyHostToDevice, s));
-  MPM_NCCL_CHECK(c, r, r.AllReduce(vote, vote + 1, 1, ncclInt32, ncclMax, r.comm, s));
-  MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + 28, vote + 1, sizeof(int), hipMemcpyDeviceToHost, s));
+  MPM_NCCL_CHECK(c, r, r.AllReduce(vote, vote_all, 1, ncclInt32, ncclMax, r.comm, s));
+  MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + PIN_LINK_VOTE, vote_all, sizeof(int), hipMemcpyDeviceToHost, s));
   MPM_HIP_CHECK(c, hipStreamSynchronize(s));
-  if (f->h_pin[28] == 0) {
-    MPM_HIP_CHECK(c, hipMemsetAsync(f->g.counters + 10, 0, 2 * sizeof(int), s));
+  if (f->h_pin[PIN_LINK_VOTE] == 0) {
+    MPM_HIP_CHECK(c, hipMemsetAsync(f->g.counters + CNT_LINK_TIMEOUT, 0, 2 * sizeof(int), s));  // (TIMEOUT and BAD)
     for (int round = 0; round < 4; ++round) {
       int seq = (int)++f->halo_seq, par = seq & 1;
       for (auto &p : f->rpeers) {
@@ -467,12 +467,12 @@ static int rccl_link_setup(mpmhip_ctx *c) {
       }
     }
     hipLaunchKernelGGL(k_link_verdict, 1, 1, 0, s, f->g.counters);
-    MPM_NCCL_CHECK(c, r, r.AllReduce(vote, vote + 1, 1, ncclInt32, ncclMax, r.comm, s));
-    MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + 28, vote + 1, sizeof(int), hipMemcpyDeviceToHost, s));
+    MPM_NCCL_CHECK(c, r, r.AllReduce(vote, vote_all, 1, ncclInt32, ncclMax, r.comm, s));
+    MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + PIN_LINK_VOTE, vote_all, sizeof(int), hipMemcpyDeviceToHost, s));
     MPM_HIP_CHECK(c, hipStreamSynchronize(s));
-    MPM_HIP_CHECK(c, hipMemsetAsync(f->g.counters + 10, 0, 2 * sizeof(int), s));
+    MPM_HIP_CHECK(c, hipMemsetAsync(f->g.counters + CNT_LINK_TIMEOUT, 0, 2 * sizeof(int), s));
   }
-  f->link_on = f->h_pin[28] == 0;
+  f->link_on = f->h_pin[PIN_LINK_VOTE] == 0;
   if (getenv("MPMHIP_VERBOSE"))
     fprintf(stderr, "[mpmhip] rank %d: halo transport %s\n", r.rank, f->link_on ? "peer-mapped buffers" : "ncclSend/ncclRecv");
   return MPMHIP_OK;
@@ -486,7 +486,6 @@ static int rccl_rebin(mpmhip_ctx *c) {
   unsigned char *mine = f->map_all + (size_t)r.rank * f->nblocks;
   if ((rc = fast_dist_rebin(c, mine))) return rc;
   MPM_NCCL_CHECK(c, r, r.AllGather(mine, f->map_all, f->nblocks, ncclUint8, r.comm, s));
-  int CH = c->movers.empty() ? 4 : 8;
   f->peers.clear();
   for (auto &p : f->rpeers) {
     hipLaunchKernelGGL(k_shared_flags, nblk(nb), TPB, 0, s, mine, f->map_all + (size_t)p.rank * f->nblocks, nb, p.flag);
@@ -506,7 +505,6 @@ static int rccl_rebin(mpmhip_ctx *c) {
     q.ghost_send = p.ghost_send; q.ghost_recv = p.ghost_recv;
     f->peers.push_back(q);
   }
-  (void)CH;
   if (f->link_want && !f->link_decided && (rc = rccl_link_setup(c))) return rc;
   for (size_t i = 0; i < f->peers.size(); ++i) {
     const RcclPeer &p = f->rpeers[i];
@@ -515,7 +513,7 @@ static int rccl_rebin(mpmhip_ctx *c) {
   }
   // fused halo for this interval?
   f->fused_halo = false;
-  if (f->fused_want && f->link_on && f->g2p_mflag == false && f->fuse_grid && f->peers.size() <= (size_t)PEER_TAB) {
+  if (f->fused_want && f->link_on && f->fuse_grid && f->peers.size() <= (size_t)PEER_TAB) {
     bool all = true, any = false;
     for (auto &q : f->peers)
       if (q.n_blocks) { any = true; all = all && peer_linked(f, q); }
@@ -529,9 +527,9 @@ static int rccl_rebin(mpmhip_ctx *c) {
       for (size_t i = 0; i < f->peers.size(); ++i)
         if (f->peers[i].n_blocks)
           hipLaunchKernelGGL(k_halo_slots, nblk(nb), TPB, 0, s, f->rpeers[i].flag, f->rpeers[i].index, nb, (int)i, f->halo_slot, f->halo_multi);
-      MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + 30, f->halo_multi, sizeof(int), hipMemcpyDeviceToHost, s));
+      MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + PIN_HALO_MULTI, f->halo_multi, sizeof(int), hipMemcpyDeviceToHost, s));
       MPM_HIP_CHECK(c, hipStreamSynchronize(s));
-      f->fused_halo = f->h_pin[30] == 0;
+      f->fused_halo = f->h_pin[PIN_HALO_MULTI] == 0;
     }
   }
   return MPMHIP_OK;
@@ -573,24 +571,20 @@ int fast_rccl_steps(mpmhip_ctx *c, float dt, int n, int64_t step_index, int rebi
     c->cur_pts = a.mesh_x ? a.mesh_x : c->mesh_points;
     c->cur_vel = a.mesh_v ? a.mesh_v : c->mesh_vel;
     c->cur_f = (a.mesh_x && a.mesh_v) ? a.mesh_f : 0.0f;
-    if (adaptive && f->dflag_pending && idx >= f->dflag_check_at) {
-      if (f->g.host_sig) {  // posted by k_post_flag: wait for THIS reduction's sequence number, then read its value
-        for (long spins = 0; (unsigned)f->h_sig[SIG_DSEQ] != f->dflag_seq; ++spins) {
-          if ((spins & 0x3ff) == 0x3ff) {
-            hipError_t e = hipStreamQuery(c->stream);
-            if (e == hipSuccess && (unsigned)f->h_sig[SIG_DSEQ] != f->dflag_seq)
-              return fail(c, MPMHIP_ERR_HIP, "rccl_steps: the reduced drift flag never reached host memory");
-            if (e != hipSuccess && e != hipErrorNotReady) MPM_HIP_CHECK(c, e);
-          }
-          std::this_thread::yield();
+    if (adaptive && f->dflag_in_flight && idx >= f->dflag_check_at) {
+      // posted by k_post_flag: wait for THIS reduction's sequence number, then read its value
+      for (long spins = 0; (unsigned)f->h_sig[SIG_DSEQ] != f->dflag_seq; ++spins) {
+        if ((spins & 0x3ff) == 0x3ff) {
+          hipError_t e = hipStreamQuery(c->stream);
+          if (e == hipSuccess && (unsigned)f->h_sig[SIG_DSEQ] != f->dflag_seq)
+            return fail(c, MPMHIP_ERR_HIP, "rccl_steps: the reduced drift flag never reached host memory");
+          if (e != hipSuccess && e != hipErrorNotReady) MPM_HIP_CHECK(c, e);
         }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        if (f->h_sig[SIG_DFLAG]) f->dist_resort = true;
-      } else {
-        MPM_HIP_CHECK(c, hipEventSynchronize(f->ev_flag));
-        if (f->h_pin[26]) f->dist_resort = true;
+        std::this_thread::yield();
       }
-      f->dflag_pending = false;
+      std::atomic_thread_fence(std::memory_order_acquire);
+      if (f->h_sig[SIG_DFLAG]) f->dist_resort = true;
+      f->dflag_in_flight = false;
     }
     bool due = adaptive ? (f->dist_resort || f->dist_since >= cap || !f->rccl_sorted) : (idx % cap == 0);
     if (due || c->caller_dirty) {
@@ -609,10 +603,9 @@ int fast_rccl_steps(mpmhip_ctx *c, float dt, int n, int64_t step_index, int rebi
       f->dist_since = 0;
       f->dist_resort = false;
       f->rccl_sorted = true;
-      if (f->dflag_pending) {  // a reduction issued before this re-sort speaks about the old order: drop it (every rank does)
-        if (!f->g.host_sig) MPM_HIP_CHECK(c, hipEventSynchronize(f->ev_flag));
-        f->dflag_pending = false;  // (host memory: the next poll waits for a newer sequence number)
-      }
+      // a reduction issued before this re-sort speaks about the old order: drop it (every rank does; the next poll waits for a
+      // newer sequence number)
+      f->dflag_in_flight = false;
     }
     f->halo_seq += 1;
     if ((rc = fast_dist_phase(c, 0, a))) return rc;
@@ -626,22 +619,19 @@ int fast_rccl_steps(mpmhip_ctx *c, float dt, int n, int64_t step_index, int rebi
     c->time = c->time + c->time_inc(dt);
     c->substeps += 1;
     f->dist_since += 1;
-    if (adaptive && !f->dflag_pending && f->dist_since % DIST_POLL == 0) {
-      MPM_NCCL_CHECK(c, f->rccl, f->rccl.AllReduce(f->g.counters + 6, f->g.counters + 7, 1, ncclInt32, ncclMax, f->rccl.comm, c->stream));
-      if (f->g.host_sig) {  // no copy + event on the stream (each costs an idle queue, see fast_step): one thread posts the result
-        hipLaunchKernelGGL(k_post_flag, 1, 1, 0, c->stream, f->g.counters + 7, f->g.host_sig, (int)++f->dflag_seq);
-      } else {
-        MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + 26, f->g.counters + 7, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        MPM_HIP_CHECK(c, hipEventRecord(f->ev_flag, c->stream));
-      }
-      f->dflag_pending = true;
+    if (adaptive && !f->dflag_in_flight && f->dist_since % DIST_POLL == 0) {
+      MPM_NCCL_CHECK(c, f->rccl, f->rccl.AllReduce(f->g.counters + CNT_DRIFT, f->g.counters + CNT_DRIFT_ALL, 1, ncclInt32, ncclMax,
+                                                   f->rccl.comm, c->stream));
+      // no copy + event on the stream (each costs an idle queue, see fast_step): one thread posts the result
+      hipLaunchKernelGGL(k_post_flag, 1, 1, 0, c->stream, f->g.counters + CNT_DRIFT_ALL, f->g.host_sig, (int)++f->dflag_seq);
+      f->dflag_in_flight = true;
       f->dflag_check_at = idx + 1 + DIST_LAG;
     }
   }
   if (f->link_on) {  // a wait that ran into its wall-clock bound computed with an incomplete halo: fail the call
-    MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + 29, f->g.counters + 10, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + PIN_LINK_TIMEOUT, f->g.counters + CNT_LINK_TIMEOUT, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     MPM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    if (f->h_pin[29]) return fail(c, MPMHIP_ERR_HIP, "rccl_steps: a peer-mapped halo never arrived (flag wait timed out)");
+    if (f->h_pin[PIN_LINK_TIMEOUT]) return fail(c, MPMHIP_ERR_HIP, "rccl_steps: a peer-mapped halo never arrived (flag wait timed out)");
   }
   return MPMHIP_OK;
 }
@@ -651,9 +641,9 @@ int64_t fast_dist_fused_halo_steps(const mpmhip_ctx *c) { return c->fast->fused_
 // the drift flag of this rank (set by the kernels when a particle is about to leave its tile margin); synchronous
 int fast_dist_drift_flag(mpmhip_ctx *c, int32_t *out) {
   FastState *f = c->fast;
-  MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + 27, f->g.counters + 6, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + PIN_DIST_DRIFT, f->g.counters + CNT_DRIFT, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   MPM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-  *out = f->h_pin[27];
+  *out = f->h_pin[PIN_DIST_DRIFT];
   return MPMHIP_OK;
 }
 

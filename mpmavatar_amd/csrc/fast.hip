@@ -45,8 +45,8 @@ __global__ __launch_bounds__(TPB) void k_grid(const int *alist, int n_A, Dims d,
   if (gp.count) {  // statistics for the algorithmic-bytes formula (N_coll, N_mov), one atomic per wavefront
     unsigned long long bc = __ballot(ncol), bm = __ballot(nmov);
     if (l == 0) {
-      if (bc) atomicAdd(g.counters + 2, __popcll(bc));
-      if (bm) atomicAdd(g.counters + 3, __popcll(bm));
+      if (bc) atomicAdd(g.counters + CNT_NCOL, __popcll(bc));
+      if (bm) atomicAdd(g.counters + CNT_NMOV, __popcll(bm));
     }
   }
 }
@@ -146,30 +146,100 @@ int flush_elements(mpmhip_ctx *c) {
   return MPMHIP_OK;
 }
 
-// what has to be cleared after the last fused substep (the buffer g points at), marking it clean
-ZeroArgs take_zero(FastState *f) {
-  // (a buffer that holds the collider field of a body at rest keeps it: col_state 2)
-  const int has_col = (f->dirty_col && f->col_state[f->par] != 2) ? 1 : 0;
-  ZeroArgs z{f->alist, f->n_A, 0, has_col, f->dirty_mov, f->g.mv, f->g.col, f->g.mov, f->g.m_flag, f->g.col_flag};
-  if (f->grid_dirty && f->n_A) z.n_wg = (f->n_A + PT / 64 - 1) / (PT / 64);
-  if (f->grid_dirty && f->col_state[f->par] == 1) f->col_state[f->par] = 0;   // (cleared by the workgroups these arguments go to)
-  f->grid_dirty = false;
+void launch_zero_blocks(hipStream_t s, const ZeroArgs &z) {
+  if (z.n_wg) hipLaunchKernelGGL(k_zero_blocks, (unsigned)z.n_wg, PT, 0, s, z);
+}
+
+// ---- AccumRing (fast_state.hpp) ----------------------------------------------------------------------------------------------
+int AccumRing::allocate(mpmhip_ctx *c, GridPtrs *g_, size_t nblocks_, bool three) {
+  g = g_; nblocks = nblocks_; nbuf = three ? 3 : 2;
+  int rc;
+  for (int i = 0; i < nbuf; ++i) {
+    if ((rc = dalloc(c, &mv[i], nblocks * GCH_MV * 64))) return rc;
+    if ((rc = dalloc(c, &mflag[i], nblocks))) return rc;
+    if ((rc = dalloc(c, &cflag[i], nblocks))) return rc;
+  }
+  if ((rc = dalloc(c, &zero_flags, nblocks))) return rc;
+  point_at(0);
+  return MPMHIP_OK;
+}
+int AccumRing::add_channels(mpmhip_ctx *c, float *(&ch)[3], int per_block, float **weight) {
+  int rc = MPMHIP_OK;
+  for (int i = 0; i < nbuf && !rc; ++i) rc = dalloc(c, &ch[i], nblocks * per_block * 64);
+  point_at(cur);
+  *weight = ch[0];
+  return rc;
+}
+void AccumRing::point_at(int k) {
+  cur = k;
+  g->mv = mv[k]; g->col = col[k]; g->mov = mov[k];
+  g->m_flag = mflag[k]; g->col_flag = cflag[k];
+}
+// the clearing of buffer k over the active list (k < 0: nothing to clear)
+ZeroArgs AccumRing::zero_args(int k, int has_col, int has_mov) const {
+  if (k < 0) return ZeroArgs{list, n_list, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
+  return ZeroArgs{list, n_list, clear_wgs(), has_col, has_mov, mv[k], col[k], mov[k], mflag[k], cflag[k]};
+}
+// what has to be cleared after the last fused substep (the current buffer), marking it clean
+ZeroArgs AccumRing::take_loaded() {
+  // (a buffer that holds the collider field of a body at rest keeps it)
+  ZeroArgs z = zero_args(cur, (loaded_col && col_field[cur] != COL_KEPT) ? 1 : 0, loaded_mov);
+  if (!is_loaded) z.n_wg = 0;
+  if (is_loaded && col_field[cur] == COL_SPLAT) col_field[cur] = COL_CLEAN;  // (cleared by the workgroups these arguments go to)
+  is_loaded = false;
   return z;
 }
-// collider fields kept for a body at rest: clear them now, over the active list as it stands (before it changes; before a body that
-// moves splats into the buffers again)
-void drop_kept_collider_fields(mpmhip_ctx *c) {
-  FastState *f = c->fast;
-  for (int k = 0; k < f->nbuf; ++k) {
-    if (f->col_state[k] != 2) continue;
-    if (f->n_A && f->col2[k]) {
+ZeroArgs AccumRing::begin_substep(hipStream_t s, bool clear_now) {
+  ZeroArgs z = take_loaded();
+  if (z.n_wg && clear_now) {
+    launch_zero_blocks(s, z);
+    z.n_wg = 0;
+  } else if (z.n_wg) {
+    point_at((cur + 1) % nbuf);
+  }
+  return z;
+}
+ZeroArgs AccumRing::begin_fused_substep() {
+  // rotate: read R = current, scatter into W = the next, clear Z = what the fused launch before this one read
+  const int R = cur;
+  const ZeroArgs z = zero_args(n_list ? fused_read : -1, fused_col, fused_mov);
+  fused_read = R; fused_col = loaded_col; fused_mov = loaded_mov;
+  is_loaded = false;
+  point_at((R + 1) % 3);
+  return z;
+}
+void AccumRing::clear_fused_read(hipStream_t s) {
+  if (fused_read < 0) return;
+  launch_zero_blocks(s, zero_args(fused_read, fused_col, fused_mov));
+  fused_read = -1;
+}
+bool AccumRing::collider_substep(bool keep) {
+  if (nbuf != 2) return false;
+  if (keep && col_field[cur] == COL_KEPT) return true;
+  col_field[cur] = keep ? COL_KEPT : COL_SPLAT;
+  return false;
+}
+void AccumRing::mark_loaded(int has_col, int has_mov) {
+  is_loaded = true;
+  loaded_col = has_col; loaded_mov = has_mov;
+}
+void AccumRing::invalidate_kept_fields(hipStream_t s) {
+  for (int k = 0; k < nbuf; ++k) {
+    if (col_field[k] != COL_KEPT) continue;
+    if (col[k]) {
       // col-only pass: an all-zero flag array stands in for the mass flags (m_flag of the buffer may be live)
-      ZeroArgs z{f->alist, f->n_A, (f->n_A + PT / 64 - 1) / (PT / 64), 1, 0, f->mv2[k], f->col2[k], f->mov2[k], f->zero_flags, f->cflag2[k]};
-      hipLaunchKernelGGL(k_zero_blocks, (unsigned)z.n_wg, PT, 0, c->stream, z);
+      ZeroArgs z = zero_args(k, 1, 0);
+      z.m_flag = zero_flags;
+      launch_zero_blocks(s, z);
     }
-    f->col_state[k] = 0;
+    col_field[k] = COL_CLEAN;
   }
 }
+AccumRing::Relist AccumRing::begin_relist(hipStream_t s) {
+  invalidate_kept_fields(s);  // (they live on the OLD active list and in the old face bins)
+  return Relist(take_loaded());
+}
+
 __global__ void k_any_nonzero(const float *v, size_t n, int *flag) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   bool nz = i < n && v[i] != 0.0f;
@@ -180,36 +250,26 @@ __global__ void k_any_nonzero(const float *v, size_t n, int *flag) {
 // the pose may have changed between calls.
 int fast_body_at_rest_begin(mpmhip_ctx *c, int n_substeps) {
   FastState *f = c->fast;
-  f->col_at_rest = false;
-  drop_kept_collider_fields(c);
-  const bool eligible = f->col_keep && n_substeps >= 16 && !c->colliders.empty() && c->num_mesh_f && c->num_mesh_v && f->nbuf == 2 && f->fuse_grid &&
-                        !c->profiling && !f->dist && c->cur_vel && !(MPMHIP_DEBUG && f->g.dbg);
+  f->acc.set_body_at_rest(false);
+  f->acc.invalidate_kept_fields(c->stream);
+  // (!f->dist: a sharded run keeps no fields)
+  const bool eligible = f->col_keep && n_substeps >= 16 && !c->colliders.empty() && c->num_mesh_f && c->num_mesh_v && f->acc.n_buffers() == 2 &&
+                        f->fuse_grid && !c->profiling && !f->dist && c->cur_vel && !(MPMHIP_DEBUG && f->g.dbg);
   if (!eligible) return MPMHIP_OK;
-  int *flag = f->g.counters + 13;
+  int *flag = f->g.counters + CNT_BODY_MOVES;
   MPM_HIP_CHECK(c, hipMemsetAsync(flag, 0, sizeof(int), c->stream));
   const size_t nm = (size_t)c->num_mesh_v * 3;
   hipLaunchKernelGGL(k_any_nonzero, (unsigned)((nm + 255) / 256), 256, 0, c->stream, c->cur_vel, nm, flag);
-  MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + 31, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + PIN_BODY_MOVES, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   MPM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-  f->col_at_rest = f->h_pin[31] == 0;
+  f->acc.set_body_at_rest(f->h_pin[PIN_BODY_MOVES] == 0);
   return MPMHIP_OK;
 }
-void fast_body_at_rest_end(mpmhip_ctx *c) { c->fast->col_at_rest = false; }   // (kept fields are dropped by whoever steps next)
-void select_buffer(FastState *f, int par) {
-  f->par = par;
-  f->g.mv = f->mv2[par]; f->g.col = f->col2[par]; f->g.mov = f->mov2[par];
-  f->g.m_flag = f->mflag2[par]; f->g.col_flag = f->cflag2[par];
-}
-// clear the accumulators now (the active list is about to change)
-void flush_grid(mpmhip_ctx *c) {
-  FastState *f = c->fast;
-  ZeroArgs z = take_zero(f);
-  if (z.n_wg) hipLaunchKernelGGL(k_zero_blocks, (unsigned)z.n_wg, PT, 0, c->stream, z);
-}
+void fast_body_at_rest_end(mpmhip_ctx *c) { c->fast->acc.set_body_at_rest(false); }   // (kept fields are dropped by whoever steps next)
 // v_out of the last (fused) substep for export_grid / stats; the accumulators stay as they are
 void materialize_grid(mpmhip_ctx *c, bool count) {
   FastState *f = c->fast;
-  if (!f->grid_dirty || !f->n_A) return;
+  if (!f->acc.loaded() || !f->n_A) return;
   GridParams gp = f->last_gp;
   gp.count = count ? 1 : 0;
   hipLaunchKernelGGL(k_grid<false>, xcd_grid((f->n_A + 3) / 4), TPB, 0, c->stream, f->alist, f->n_A, f->d, f->g, gp, f->last_bcl);
@@ -258,17 +318,10 @@ int fast_init(mpmhip_ctx *c) {
   if ((rc = dalloc(c, &f->adj_cnt, (size_t)d.n_v + 1))) return rc;
   if ((rc = dalloc(c, &f->order, (size_t)d.n_p))) return rc;
   if ((rc = dalloc(c, &f->iota, (size_t)d.n_p))) return rc;
-  f->nbuf = (d.n_e == 0 && d.n_v == 0 && d.n_t > 0) ? 3 : 2;
-  for (int i = 0; i < f->nbuf; ++i) {
-    if ((rc = dalloc(c, &f->mv2[i], f->nblocks * GCH_MV * 64))) return rc;
-    if ((rc = dalloc(c, &f->mflag2[i], f->nblocks))) return rc;
-    if ((rc = dalloc(c, &f->cflag2[i], f->nblocks))) return rc;
-  }
-  select_buffer(f, 0);
+  if ((rc = f->acc.allocate(c, &f->g, f->nblocks, d.n_e == 0 && d.n_v == 0 && d.n_t > 0))) return rc;
   if ((rc = dalloc(c, &f->g.vout, f->nblocks * GCH_VOUT * 64))) return rc;
   if ((rc = dalloc(c, &f->g.counters, CNT_N))) return rc;
   if ((rc = dalloc(c, &f->pack_done, (size_t)DONE_SHARDS * DONE_STRIDE))) return rc;
-  if ((rc = dalloc(c, &f->zero_flags, f->nblocks))) return rc;
   // one allocation, one memset per re-sort: [particle-block flags | active-block flags | device counts]
   static_assert(RC_N <= 64, "device counts of a re-sort");
   f->fc_tiles = (int)((f->nblocks + FC_TILE - 1) / FC_TILE);
@@ -301,16 +354,14 @@ int fast_init(mpmhip_ctx *c) {
     f->g.stagger = std::max(0, u); f->g.stagger_groups = std::max(1, gr); f->g.stagger_first = std::max(0, first);
     f->stagger_auto = -1;  // forced
   }
-  if (const char *e = getenv("MPMHIP_G2P_MFLAG")) f->g2p_mflag = atoi(e) != 0;
-  MPM_HIP_CHECK(c, hipHostMalloc((void **)&f->h_pin, 64 * sizeof(int), hipHostMallocDefault));
-  MPM_HIP_CHECK(c, hipEventCreateWithFlags(&f->ev_flag, hipEventDisableTiming));
+  MPM_HIP_CHECK(c, hipHostMalloc((void **)&f->h_pin, PIN_N * sizeof(int), hipHostMallocDefault));
   {
     int *hs = nullptr, *ds = nullptr;
     MPM_HIP_CHECK(c, hipHostMalloc((void **)&hs, SIG_WORDS * sizeof(int), hipHostMallocMapped));
     memset(hs, 0, SIG_WORDS * sizeof(int));
     MPM_HIP_CHECK(c, hipHostGetDevicePointer((void **)&ds, hs, 0));
     f->h_sig = hs;
-    f->g.host_sig = getenv("MPMHIP_FLAG_COPY") ? nullptr : ds;  // MPMHIP_FLAG_COPY=1: the former copy + event poll (A/B)
+    f->g.host_sig = ds;
     if (const char *e = getenv("MPMHIP_HOST_LEAD")) f->host_lead = std::min(std::max(1, atoi(e)), 12);  // (ring of 16 entries)
     f->g.lookahead = DRIFT_LOOKAHEAD;
     if (const char *e = getenv("MPMHIP_DRIFT_LOOKAHEAD")) f->g.lookahead = (float)atof(e);
@@ -330,7 +381,6 @@ void fast_destroy(mpmhip_ctx *c) {
   if (f->h_pin) (void)hipHostFree(f->h_pin);
   if (f->h_sig) (void)hipHostFree((void *)f->h_sig);
   f->h_ranges.release(); f->h_plist.release(); f->h_chunks.release(); f->h_chunks_g.release();
-  if (f->ev_flag) (void)hipEventDestroy(f->ev_flag);
   delete f;
   c->fast = nullptr;
 }
@@ -349,11 +399,7 @@ int fast_add_collider_storage(mpmhip_ctx *c, MeshCollider &mc) {
   if ((rc = dalloc(c, &f->fiota, (size_t)nf))) return rc;
   if ((rc = dalloc(c, &f->fb_start, f->nblocks))) return rc;
   if ((rc = dalloc(c, &f->fb_cnt, f->nblocks))) return rc;
-  for (int i = 0; i < f->nbuf; ++i)
-    if ((rc = dalloc(c, &f->col2[i], f->nblocks * GCH_COL * 64))) return rc;
-  select_buffer(f, f->par);
-  mc.weight = f->col2[0];
-  return MPMHIP_OK;
+  return f->acc.add_collider_channels(c, &mc.weight);
 }
 
 int fast_add_mover_storage(mpmhip_ctx *c, Mover &mv) {
@@ -362,11 +408,7 @@ int fast_add_mover_storage(mpmhip_ctx *c, Mover &mv) {
     mv.weight = c->movers[0].weight;  // touched nodes: a second one repeats the first one's result exactly
     return MPMHIP_OK;
   }
-  int rc = MPMHIP_OK;
-  for (int i = 0; i < f->nbuf && !rc; ++i) rc = dalloc(c, &f->mov2[i], f->nblocks * GCH_MOV * 64);
-  select_buffer(f, f->par);
-  mv.weight = f->mov2[0];
-  return rc;
+  return f->acc.add_mover_channels(c, &mv.weight);
 }
 
 // One substep = three phases; the multi-GPU driver interleaves its exchanges between them:
@@ -382,8 +424,8 @@ static bool g2p2g_ok(const mpmhip_ctx *c) {
   // ... and, as the kernel stands, where one round of workgroups holds the whole scene: hipcc gives the fused kernel 212-227 VGPRs
   // (two wavefronts per SIMD = 512 workgroup slots; either half alone needs 116-124, profiles/r04_experiments.md), which a scene
   // of more chunks pays for with more than it saves (block-512k -8 %, garment-120k-iso -11 %; cube-8k +23 %)
-  return f->g2p2g && f->nbuf == 3 && !f->dist && !c->profiling && d.n_e == 0 && d.n_v == 0 && d.n_t > 0 && f->fuse_trad && f->fuse_grid &&
-         !f->g.halo.slot && !f->g2p_mflag && !(MPMHIP_DEBUG && f->g.dbg) && f->n_chunks > 0 && f->n_chunks <= f->g2p2g_max_chunks;
+  return f->g2p2g && f->acc.n_buffers() == 3 && !f->dist && !c->profiling && d.n_e == 0 && d.n_v == 0 && d.n_t > 0 && f->fuse_trad && f->fuse_grid &&
+         !f->g.halo.slot && !(MPMHIP_DEBUG && f->g.dbg) && f->n_chunks > 0 && f->n_chunks <= f->g2p2g_max_chunks;
 }
 // the deferred g2p of the last substep as a launch of its own (anything that reads or re-orders the particles comes here first),
 // and the clearing of the buffer the last fused launch read
@@ -396,52 +438,34 @@ int flush_g2p(mpmhip_ctx *c) {
     }
     f->g2p_pending = false;
   }
-  if (f->clear_later >= 0) {
-    const int k = f->clear_later;
-    ZeroArgs z{f->alist, f->n_A, 0, f->cl_col, f->cl_mov, f->mv2[k], f->col2[k], f->mov2[k], f->mflag2[k], f->cflag2[k]};
-    if (f->n_A) {
-      z.n_wg = (f->n_A + PT / 64 - 1) / (PT / 64);
-      hipLaunchKernelGGL(k_zero_blocks, (unsigned)z.n_wg, PT, 0, c->stream, z);
-    }
-    f->clear_later = -1;
-  }
+  f->acc.clear_fused_read(c->stream);
   return MPMHIP_OK;
 }
 
-// Look at the drift flags the device has posted (ring in pinned host memory, or the copied flag of contexts without one) and turn a
-// raised flag into "re-sort before the next substep" (steps_since_rebin = 1 << 30).  Called once per substep, at the head of
-// step_phase_a.
+// Look at the drift flags the device has posted (ring in pinned host memory) and turn a raised flag into "re-sort before the next
+// substep" (steps_since_rebin = 1 << 30).  Called once per substep, at the head of step_phase_a.
 static int poll_drift_flags(mpmhip_ctx *c) {
   FastState *f = c->fast;
-  hipStream_t s = c->stream;
-  {
-    if (f->g.host_sig) {
-      // the kernels report progress and their flags into pinned host memory (k_p2g): no stream operation here.  Before
-      // substep s the host waits until substep s - host_lead has started and decides with THAT substep's entry: it keeps
-      // host_lead substeps queued (enough to hide its launch latency) and no more, and a warning takes effect exactly
-      // host_lead substeps after the launch that posted it (the copy + event scheme: 8-16) -- inside the look-ahead.
-      const unsigned e = f->sig_seq + 1u - (unsigned)f->host_lead;  // the substep whose ring entry decides now
-      bool arrived = true;
-      for (long spins = 0; (int)((unsigned)f->h_sig[SIG_PROGRESS] - e) < 0; ++spins) {
-        if ((spins & 0x3ff) == 0x3ff) {
-          hipError_t q = hipStreamQuery(s);
-          if (q == hipSuccess) { arrived = (int)((unsigned)f->h_sig[SIG_PROGRESS] - e) >= 0; break; }  // nothing in flight any more
-          if (q != hipErrorNotReady) MPM_HIP_CHECK(c, q);
-        }
-        std::this_thread::yield();
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
-      if (arrived && (int)(e - f->sig_at_rebin) > 0) {  // an entry written after the last re-sort
-        unsigned v = (unsigned)f->h_sig[SIG_RING0 + (e & (unsigned)(SIG_RING_N - 1))];
-        if ((v >> 2) == (e & 0x3fffffffu)) {
-          if (v & 2u) f->face_flag_seen = true;
-          if ((v & 1u) && f->adaptive_rebin) f->steps_since_rebin = 1 << 30;
-        }
-      }
-    } else if (f->flag_pending && (f->steps_since_rebin & f->poll_mask) == 0) {
-      MPM_HIP_CHECK(c, hipEventSynchronize(f->ev_flag));
-      f->flag_pending = false;
-      if (f->h_pin[24] && f->adaptive_rebin) f->steps_since_rebin = 1 << 30;
+  // the kernels report progress and their flags into pinned host memory (k_p2g): no stream operation here.  Before
+  // substep s the host waits until substep s - host_lead has started and decides with THAT substep's entry: it keeps
+  // host_lead substeps queued (enough to hide its launch latency) and no more, and a warning takes effect exactly
+  // host_lead substeps after the launch that posted it -- inside the look-ahead.
+  const unsigned e = f->sig_seq + 1u - (unsigned)f->host_lead;  // the substep whose ring entry decides now
+  bool arrived = true;
+  for (long spins = 0; (int)((unsigned)f->h_sig[SIG_PROGRESS] - e) < 0; ++spins) {
+    if ((spins & 0x3ff) == 0x3ff) {
+      hipError_t q = hipStreamQuery(c->stream);
+      if (q == hipSuccess) { arrived = (int)((unsigned)f->h_sig[SIG_PROGRESS] - e) >= 0; break; }  // nothing in flight any more
+      if (q != hipErrorNotReady) MPM_HIP_CHECK(c, q);
+    }
+    std::this_thread::yield();
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  if (arrived && (int)(e - f->sig_at_rebin) > 0) {  // an entry written after the last re-sort
+    unsigned v = (unsigned)f->h_sig[SIG_RING0 + (e & (unsigned)(SIG_RING_N - 1))];
+    if ((v >> 2) == (e & 0x3fffffffu)) {
+      if (v & 2u) f->face_flag_seen = true;
+      if ((v & 1u) && f->adaptive_rebin) f->steps_since_rebin = 1 << 30;
     }
   }
   return MPMHIP_OK;
@@ -452,13 +476,12 @@ int step_phase_a(mpmhip_ctx *c, const StepArgs &a) {
   const Dims &d = f->d;
   hipStream_t s = c->stream;
   int rc;
-  (void)rc; (void)d; (void)s;
   if (c->caller_dirty) {
     if (f->dist) return fail(c, MPMHIP_ERR_STATE, "dist mode: call mpmhip_dist_rebin after (re)binding the state");
     if ((rc = do_import(c))) return rc;
   }
   const float dt = a.dt;
-  if (!f->col_at_rest) drop_kept_collider_fields(c);   // (fields kept by an mpmhip_steps call whose body was at rest: this body may move)
+  if (!f->acc.body_at_rest()) f->acc.invalidate_kept_fields(s);   // (fields kept by an mpmhip_steps call whose body was at rest: this body may move)
   // pre-p2g particle operations, mpm_solver.py:260-279 (impulses first, then velocity modifiers)
   if (f->g2p_pending && (!g2p2g_ok(c) || !c->pre.empty() || dt != f->pend_dt)) flush_g2p(c);
   if (!c->pre.empty() && d.n_p) {
@@ -472,20 +495,14 @@ int step_phase_a(mpmhip_ctx *c, const StepArgs &a) {
       }
   }
   if (!f->dist) {
-    // Drift flag raised by g2p / element finalise / collider splat.  It is copied back every 8 substeps; before
-    // the next copy is issued the host waits for the previous one, which also bounds how far the host may run
-    // ahead of the GPU (<= 16 substeps) -- otherwise a fused mpmhip_steps(n) would have enqueued all n substeps
+    // Drift flag raised by g2p / element finalise / collider splat.  Reading it also bounds how far the host may run
+    // ahead of the GPU (host_lead substeps) -- otherwise a fused mpmhip_steps(n) would have enqueued all n substeps
     // long before the first flag arrives.
     if ((rc = poll_drift_flags(c))) return rc;
     if (f->steps_since_rebin >= f->rebin_interval) {
       ScopedPhase ph(c, "rebin");
       // predictive sort: aim at the middle of the next interval, estimated from the one that just ended
-      if (f->true_since_rebin > 0) {
-        f->lead_steps = std::min(std::max(0.5f * (float)f->true_since_rebin, 4.0f), 48.0f);
-        // fast material (short intervals): look at the flag more often, so that the host's lag stays well inside the
-        // 20-substep early warning and nothing outruns the active blocks
-        f->poll_mask = f->true_since_rebin <= 24 ? 1 : (f->true_since_rebin <= 48 ? 3 : 7);
-      }
+      if (f->true_since_rebin > 0) f->lead_steps = std::min(std::max(0.5f * (float)f->true_since_rebin, 4.0f), 48.0f);
       f->last_dt = dt;
       if ((rc = rebin(c))) return rc;
       f->true_since_rebin = 0;
@@ -525,32 +542,11 @@ int step_phase_a(mpmhip_ctx *c, const StepArgs &a) {
   const bool do_g2p2g = f->g2p_pending && !jt_tile;  // (pending survives a re-sort decision above only when none happened)
   if (f->g2p_pending && !do_g2p2g) flush_g2p(c);
   GridRead rd{f->g.mv, f->g.col, f->g.mov, f->g.col_flag};  // (fused launch) the buffer the deferred g2p reads: the current one
-  if (do_g2p2g) {
-    // rotate: read R = current, scatter into W = the next, clear Z = what the fused launch before this one read
-    const int R = f->par, Z = f->clear_later;
-    sa.z = ZeroArgs{f->alist, f->n_A, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (Z >= 0 && f->n_A) {
-      sa.z = ZeroArgs{f->alist, f->n_A, (f->n_A + PT / 64 - 1) / (PT / 64), f->cl_col, f->cl_mov, f->mv2[Z], f->col2[Z], f->mov2[Z],
-                      f->mflag2[Z], f->cflag2[Z]};
-    }
-    f->clear_later = R; f->cl_col = f->dirty_col; f->cl_mov = f->dirty_mov;
-    f->grid_dirty = false;
-    select_buffer(f, (R + 1) % 3);
-  } else
-  sa.z = take_zero(f);
-  if (sa.z.n_wg && !do_g2p2g) {
-    if (c->profiling) {  // profiling runs keep one launch per reference phase: clear now
-      hipLaunchKernelGGL(k_zero_blocks, (unsigned)sa.z.n_wg, PT, 0, s, sa.z);
-      sa.z.n_wg = 0;
-    } else {
-      select_buffer(f, (f->par + 1) % f->nbuf);
-    }
-  }
-  // a body at rest whose collider field this buffer already holds (col_state 2): no splat workgroups in this substep
-  bool col_kept = false;
-  if (has_col && f->col_at_rest && f->nbuf == 2 && !c->profiling && f->col_state[f->par] == 2) {
+  // (profiling runs keep one launch per reference phase: they clear with a launch of their own)
+  sa.z = do_g2p2g ? f->acc.begin_fused_substep() : f->acc.begin_substep(s, c->profiling);
+  // a body at rest whose collider field the buffer already holds: no splat workgroups in this substep
+  if (has_col && f->acc.collider_substep(f->acc.body_at_rest() && !c->profiling)) {
     sa.n_fbins = 0;
-    col_kept = true;
     f->n_col_kept += 1;
   }
   // cloth scenes of the production loop: the splat's first pass rides in front of the stress launch (col_splat_wg)
@@ -629,7 +625,6 @@ int step_phase_a(mpmhip_ctx *c, const StepArgs &a) {
     if (f->n_chunks || sa.n_extra || sa.z.n_wg || sa.pack.n_wg)
       launch_p2g(c, trad_fused, jt_tile, xcd_grid(f->n_chunks) + (unsigned)(sa.n_extra + sa.z.n_wg + sa.pack.n_wg), f->n_chunks, dt, sa, tp);
   }
-  if (has_col && !col_kept && f->nbuf == 2) f->col_state[f->par] = (f->col_at_rest && !c->profiling) ? 2 : 1;
   return MPMHIP_OK;
 }
 
@@ -650,8 +645,6 @@ int step_phase_b(mpmhip_ctx *c, const StepArgs &a) {
   FastState *f = c->fast;
   const Dims &d = f->d;
   hipStream_t s = c->stream;
-  int rc;
-  (void)rc; (void)d; (void)s;
   const float dt = a.dt;
   GridParams gp;
   BCList bcl;
@@ -673,34 +666,23 @@ int step_phase_b(mpmhip_ctx *c, const StepArgs &a) {
     if (f->n_chunks_g) launch_g2p(c, fused, f->g2p_two_pass, dt, gp, bcl);
   }
   if (fused) {
-    f->grid_dirty = true;
-    f->dirty_col = gp.has_col;
-    f->dirty_mov = gp.has_mov && gp.mov_on;
+    f->acc.mark_loaded(gp.has_col, gp.has_mov && gp.mov_on);
     f->last_gp = gp;
     f->last_bcl = bcl;
   }
   return MPMHIP_OK;
 }
 
-int step_phase_c(mpmhip_ctx *c, const StepArgs &a) {
+int step_phase_c(mpmhip_ctx *c, const StepArgs &) {
   FastState *f = c->fast;
-  const Dims &d = f->d;
-  hipStream_t s = c->stream;
-  int rc;
-  (void)rc; (void)d; (void)s;
   // unprofiled: the element finalize is deferred into the next substep's stress kernel (k_stress_elem<true>); multi-GPU
   // ranks have unpacked their ghost vertices by now, so the same holds there
-  f->elem_pending = d.n_e > 0;
+  f->elem_pending = f->d.n_e > 0;
   if (c->profiling || (f->g.dbg & 64)) {
     ScopedPhase ph(c, "g2p_e");
     flush_elements(c);
   }
   f->steps_since_rebin += 1;
-  if (!f->dist && !f->g.host_sig && !f->flag_pending && (f->steps_since_rebin & f->poll_mask) == 0) {
-    MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + 24, f->g.counters + 6, sizeof(int), hipMemcpyDeviceToHost, s));
-    MPM_HIP_CHECK(c, hipEventRecord(f->ev_flag, s));
-    f->flag_pending = true;
-  }
   c->internal_dirty = true;
   MPM_HIP_CHECK(c, hipGetLastError());
   return MPMHIP_OK;
@@ -780,24 +762,25 @@ int fast_stats(mpmhip_ctx *c, mpmhip_stats *out) {
   out->p2g_tile_in_use = f->p2g_fixed_now ? MPMHIP_P2G_TILE_FIXED : MPMHIP_P2G_TILE_F64;
   out->kept_collider_substeps = (int32_t)std::min<int64_t>(f->n_col_kept, 0x7fffffff);
   out->n_active_blocks = f->n_A;
-  int *dcnt = f->g.counters + 4;
-  if (f->grid_dirty) {  // fused substeps do not count collider / mover nodes: count the last substep now
-    MPM_HIP_CHECK(c, hipMemsetAsync(f->g.counters + 2, 0, 2 * sizeof(int), c->stream));
+  int *dcnt = f->g.counters + CNT_ACTIVE;
+  if (f->acc.loaded()) {  // fused substeps do not count collider / mover nodes: count the last substep now
+    MPM_HIP_CHECK(c, hipMemsetAsync(f->g.counters + CNT_NCOL, 0, 2 * sizeof(int), c->stream));  // (NCOL and NMOV)
     materialize_grid(c, true);
     f->stat_steps = 1;
   }
   MPM_HIP_CHECK(c, hipMemsetAsync(dcnt, 0, sizeof(int), c->stream));
   if (f->n_A) hipLaunchKernelGGL(k_count_active, (unsigned)((f->n_A + 3) / 4), TPB, 0, c->stream, f->alist, f->n_A, f->g, dcnt);
-  MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + 8, f->g.counters, 8 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  const int *h = f->h_pin + PIN_STATS;
+  MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + PIN_STATS, f->g.counters, CNT_STATS_N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   MPM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-  out->n_fallback_particles = f->h_pin[8];
-  out->n_dropped = f->h_pin[9];  // contributions outside the active blocks (must stay 0)
-  out->n_active_nodes = f->h_pin[12];
+  out->n_fallback_particles = h[CNT_FALLBACK];
+  out->n_dropped = h[CNT_DROPPED];  // contributions outside the active blocks (must stay 0)
+  out->n_active_nodes = h[CNT_ACTIVE];
   if (f->stat_steps > 0) {  // per-substep averages since the previous call
-    out->n_collider_nodes = (int)(f->h_pin[10] / f->stat_steps);
-    out->n_mover_nodes = (int)(f->h_pin[11] / f->stat_steps);
+    out->n_collider_nodes = (int)(h[CNT_NCOL] / f->stat_steps);
+    out->n_mover_nodes = (int)(h[CNT_NMOV] / f->stat_steps);
   }
-  MPM_HIP_CHECK(c, hipMemsetAsync(f->g.counters + 2, 0, 2 * sizeof(int), c->stream));
+  MPM_HIP_CHECK(c, hipMemsetAsync(f->g.counters + CNT_NCOL, 0, 2 * sizeof(int), c->stream));
   f->stat_steps = 0;
   return MPMHIP_OK;
 }

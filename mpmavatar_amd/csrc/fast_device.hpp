@@ -260,14 +260,30 @@ constexpr int FC_TILE = 1024, FC_GROUP = 16;
 // host-mapped signal words (FastState::h_sig / GridPtrs::host_sig)
 enum { SIG_PROGRESS = 1, SIG_DFLAG = 2, SIG_DSEQ = 3, SIG_RING0 = 8, SIG_RING_N = 16, SIG_WORDS = 32 };
 static_assert(SIG_RING0 + SIG_RING_N <= SIG_WORDS && (SIG_RING_N & (SIG_RING_N - 1)) == 0, "signal ring must fit its buffer");
-// device counters (GridPtrs::counters): [0] particles outside their tile margin, [1] dropped contributions, [2] [3] collider /
-// mover node counts, [4] active nodes, [5] a body face left its bin's tile (sticky), [6] drift flag (sticky; dist loops and the
-// copy + event scheme read it), [7] all-reduced drift flag, [8] [9] experiment counters, [10]-[12] peer links,
-// [CNT_PAR0 + 2 * parity + {0, 1}] the same two flags per substep parity: the kernels of substep s raise slot s & 1 and the
-// p2g launch of substep s + 1 posts and clears it, so a ring entry holds exactly the flags of ONE finished substep (a plain
-// snapshot of the sticky flags raced with the workgroups of the posting launch that raise them)
-enum { CNT_FACE = 5, CNT_DRIFT = 6, CNT_PAR0 = 16, CNT_MMIN = 24, CNT_MMAX = 25, CNT_NSEL = 26, CNT_N = 32 };  // (MMIN / MMAX: smallest positive / largest
-                                                                                             // particle mass as float bits, k_mass_span)
+// device counters (GridPtrs::counters), one name per slot in use.  CNT_FACE / CNT_DRIFT are sticky (cleared by a face sort / a
+// re-sort); the dist loops read CNT_DRIFT and all-reduce it into CNT_DRIFT_ALL.  CNT_PAR0 + 2 * parity + {0, 1}: the same two
+// flags per substep parity: the kernels of substep s raise slot s & 1 and the p2g launch of substep s + 1 posts and clears it, so
+// a ring entry holds exactly the flags of ONE finished substep (a plain snapshot of the sticky flags raced with the workgroups
+// of the posting launch that raise them).  Slots that the host copies or clears as a RANGE are adjacent on purpose; the
+// static_asserts below (and those beside the copies) hold the layout to it.
+enum {
+  CNT_FALLBACK = 0, CNT_DROPPED = 1,  // particles outside their tile margin; contributions to a block that is not active (must stay 0)
+  CNT_NCOL = 2, CNT_NMOV = 3,         // collider / mover nodes: counted by the stand-alone grid stage, cleared together
+  CNT_ACTIVE = 4,                     // nodes with mass (mpmhip_get_stats)
+  CNT_FACE = 5, CNT_DRIFT = 6,        // a body face left its bin's tile; a particle is about to leave its tile margin
+  CNT_DRIFT_ALL = 7,                  // the ranks' drift flags, max-reduced
+  CNT_EXP0 = 8, CNT_EXP1 = 9,         // two experiment counters (p2g)
+  CNT_LINK_TIMEOUT = 10, CNT_LINK_BAD = 11,    // peer links: a flag wait ran into its wall-clock bound; words that arrived wrong (cleared together)
+  CNT_LINK_VOTE = 12, CNT_LINK_VOTE_ALL = 13,  // this rank's verdict on its links; the ranks' verdicts max-reduced
+  CNT_BODY_MOVES = 14,                // some vertex of the body mesh has a velocity (fast_body_at_rest_begin)
+  CNT_PAR0 = 16,
+  CNT_MMIN = 24, CNT_MMAX = 25, CNT_NSEL = 26,  // smallest positive / largest particle mass as float bits, particles with selection != 0
+  CNT_N = 32                                    // (k_mass_span): read back together, MMAX and NSEL reset together
+};
+constexpr int CNT_STATS_N = 8;   // mpmhip_get_stats reads [CNT_FALLBACK, CNT_DRIFT_ALL] in one copy
+static_assert(CNT_NCOL + 1 == CNT_NMOV && CNT_LINK_TIMEOUT + 1 == CNT_LINK_BAD && CNT_LINK_VOTE + 1 == CNT_LINK_VOTE_ALL &&
+              CNT_MMIN + 1 == CNT_MMAX && CNT_MMAX + 1 == CNT_NSEL, "counter slots that are copied or cleared as one range");
+static_assert(CNT_ACTIVE < CNT_STATS_N && CNT_BODY_MOVES < CNT_PAR0 && CNT_PAR0 + 4 <= CNT_MMIN && CNT_NSEL < CNT_N, "counter layout");
 
 // Fused halo add (multi-GPU, peer-mapped halos): k_g2p<.., HALO = true> adds the neighbour rank's contribution to a shared
 // block while it stages its tile -- own accumulator + the value the neighbour's pack stored into this rank's arena -- instead
@@ -288,7 +304,7 @@ struct GridPtrs {
   const int *ab_flag;
   int *col_flag;    // [block] 1 = the body-face splat may have written this block's collider channels this substep
   int *m_flag;      // [block] 1 = p2g (or a halo sum) may have written this block's mass / momentum this substep
-  int *counters;    // [0] particles outside their tile margin, [1] dropped contributions (inactive block)
+  int *counters;    // [CNT_N], see the CNT_* slots above
   int *host_sig;    // host-mapped pinned memory: [SIG_PROGRESS] step_id of the newest k_p2g launch that started, [SIG_RING0 +
   int step_id;      // (step_id & 15)] the flags of substep step_id - 1 (see k_p2g); [SIG_DFLAG], [SIG_DSEQ] the sharded loop's
                     // reduced flag and its sequence number (k_post_flag)
@@ -558,7 +574,7 @@ __device__ __forceinline__ int tab_peer(const Tab &t, int wg) {
 // ---- peer links: flags and data in fine-grained memory of the RECEIVING rank, mapped into the sender with HIP IPC ----------
 // Producer: every thread fences its stores at system scope, the workgroup counts itself done, the last one to do so stores
 // the flag with release semantics.  Consumer: one thread per workgroup polls the flag (acquire, system scope) with a
-// wall-clock bound, so that a lost signal fails the run (counters[10]) instead of hanging the GPU.
+// wall-clock bound, so that a lost signal fails the run (CNT_LINK_TIMEOUT) instead of hanging the GPU.
 constexpr long long LINK_TIMEOUT_TICKS = 20ll * 100000000ll;    // wall_clock64() ticks at 100 MHz: 20 s in a substep,
 constexpr long long LINK_HANDSHAKE_TICKS = 3ll * 100000000ll;   // 3 s in the set-up handshake (failure = fall back to send/recv)
 __device__ __forceinline__ void link_signal(int *cnt, int n_wg, int *flag, int seq) {

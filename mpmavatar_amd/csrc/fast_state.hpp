@@ -79,6 +79,95 @@ struct RcclPeer {  // one neighbour rank: static ghost lists + per-re-sort share
 };
 constexpr int LINK_DATA0 = 32, LINK_FLAG_STRIDE = 16;
 
+// Pinned host scratch (FastState::h_pin): where the read-backs behind the host's waits land.  One name per slot; a block is
+// [first, first + its _N).  The slots are laid out one after the other, so no two can share a word; the assert keeps that true
+// if one is ever placed by hand.
+constexpr int PIN_SCAN_N = 2, PIN_STATS_N = CNT_STATS_N, PIN_RCNT_N = RC_N, PIN_MASS_N = 3;
+enum {
+  PIN_SCAN = 0,                          // scan_flags: the two addends of the total
+  PIN_STATS = PIN_SCAN + PIN_SCAN_N,     // fast_stats: the first CNT_STATS_N device counters
+  PIN_ADJ_K = PIN_STATS + PIN_STATS_N,   // do_import: width of the vertex adjacency
+  PIN_DIST_DRIFT,                        // fast_dist_drift_flag: this rank's CNT_DRIFT
+  PIN_LINK_VOTE,                         // rccl_link_setup: CNT_LINK_VOTE_ALL
+  PIN_LINK_TIMEOUT,                      // fast_rccl_steps: CNT_LINK_TIMEOUT
+  PIN_HALO_MULTI,                        // rccl_rebin: a block shared with more than one peer (no fused halo)
+  PIN_BODY_MOVES,                        // fast_body_at_rest_begin: CNT_BODY_MOVES
+  PIN_RCNT,                              // rebin: the counts of the re-sort (RC_*)
+  PIN_MASS = PIN_RCNT + PIN_RCNT_N,      // rebin: CNT_MMIN, CNT_MMAX, CNT_NSEL
+  PIN_N = PIN_MASS + PIN_MASS_N
+};
+static_assert(PIN_SCAN + PIN_SCAN_N <= PIN_STATS && PIN_STATS + PIN_STATS_N <= PIN_ADJ_K && PIN_ADJ_K < PIN_DIST_DRIFT &&
+              PIN_BODY_MOVES < PIN_RCNT && PIN_RCNT + PIN_RCNT_N <= PIN_MASS && PIN_MASS + PIN_MASS_N <= PIN_N,
+              "blocks of the pinned scratch overlap");
+
+// The grid accumulators and everything the host knows about their contents.  There are two buffers (three for scenes that can run
+// the fused g2p -> p2g launch, k_g2p2g: read / write / clear); GridPtrs' {mv, col, mov, m_flag, col_flag} point at the current one.
+// A fused substep leaves the accumulators of the active blocks LOADED (g2p only read them): the next substep scatters into the
+// other buffer and clears the loaded one with extra workgroups of its own launches (the ZeroArgs handed out here), and whoever
+// is about to change the active list clears first.
+// A body AT REST inside one mpmhip_steps call (mesh_v == 0 for every vertex: checked once per call, fast_body_at_rest_begin): its
+// collider field -- weight, weight * velocity, weight * normal per node -- is the same in every substep, so it is splatted ONCE into
+// each of the two buffers and then KEPT: no splat workgroups, no clearing of the collider channels, until the particle order (the
+// face bins, the active list) changes, the body may move again, or the call ends (invalidate_kept_fields).
+// All of that state is private: callers say what happens to the buffers, and the active list the clearing runs over can only be
+// replaced through begin_relist(), which drops the kept fields and hands back the pending clearing first.
+class AccumRing {
+ public:
+  // begin_relist()'s receipt: the clearing the caller's next launch has to carry, and the only key to end_relist()
+  class Relist {
+    friend class AccumRing;
+    explicit Relist(const ZeroArgs &z_) : z(z_) {}
+   public:
+    const ZeroArgs z;
+  };
+  int allocate(mpmhip_ctx *c, GridPtrs *g, size_t nblocks, bool three);
+  // (weight: channel 0 of buffer 0, for the context's bookkeeping)
+  int add_collider_channels(mpmhip_ctx *c, float **weight) { return add_channels(c, col, GCH_COL, weight); }
+  int add_mover_channels(mpmhip_ctx *c, float **weight) { return add_channels(c, mov, GCH_MOV, weight); }
+  int n_buffers() const { return nbuf; }
+  bool loaded() const { return is_loaded; }  // the current buffer holds the last fused substep's accumulators
+  bool body_at_rest() const { return at_rest; }
+  void set_body_at_rest(bool r) { at_rest = r; }
+  // Head of a substep: the clearing its launches carry for what the last one left loaded.  With something to clear the ring
+  // advances to the other buffer; clear_now (one launch per phase: profiling) clears with a launch of its own and stays instead.
+  ZeroArgs begin_substep(hipStream_t s, bool clear_now);
+  // Head of a substep whose launch also runs the deferred g2p of the last one (k_g2p2g): that reads the current buffer, p2g
+  // scatters into the next, and the clearing handed back is of the buffer the fused launch BEFORE this one read.
+  ZeroArgs begin_fused_substep();
+  void clear_fused_read(hipStream_t s);  // the sequence of fused launches ends: clear what the last one read now
+  // This substep has a collider field.  true: the current buffer already holds the field of the body at rest, no splat
+  // workgroups.  Otherwise the launch splats it; `keep` (the body is at rest and the run may keep fields) keeps it from now on.
+  bool collider_substep(bool keep);
+  void mark_loaded(int has_col, int has_mov);  // a fused substep has been issued into the current buffer
+  // kept collider fields are no longer valid: clear them now, over the active list as it stands
+  void invalidate_kept_fields(hipStream_t s);
+  // The active list (or the face bins) is about to change: kept fields are dropped and the pending clearing of the old list
+  // is handed back; end_relist() installs the new list.
+  Relist begin_relist(hipStream_t s);
+  void end_relist(const Relist &, const int *alist, int n_A) { list = alist; n_list = n_A; }
+
+ private:
+  enum ColField { COL_CLEAN, COL_SPLAT, COL_KEPT };  // SPLAT: this substep's, cleared by the next launch's clearing workgroups as ever
+  int clear_wgs() const { return (n_list + PT / 64 - 1) / (PT / 64); }
+  ZeroArgs zero_args(int k, int has_col, int has_mov) const;
+  ZeroArgs take_loaded();
+  int add_channels(mpmhip_ctx *c, float *(&ch)[3], int per_block, float **weight);
+  void point_at(int k);
+  GridPtrs *g = nullptr;
+  size_t nblocks = 0;
+  float *mv[3] = {nullptr, nullptr, nullptr}, *col[3] = {nullptr, nullptr, nullptr}, *mov[3] = {nullptr, nullptr, nullptr};
+  int *mflag[3] = {nullptr, nullptr, nullptr}, *cflag[3] = {nullptr, nullptr, nullptr};
+  int *zero_flags = nullptr;  // [blocks] zeros: stands in for the mass flags where only the collider channels are cleared
+  int nbuf = 2, cur = 0;
+  const int *list = nullptr;  // the active list the contents of the buffers live on
+  int n_list = 0;
+  bool is_loaded = false;
+  int loaded_col = 0, loaded_mov = 0;  // ... with collider / mover channels
+  bool at_rest = false;                // this mpmhip_steps call's body does not move
+  ColField col_field[3] = {COL_CLEAN, COL_CLEAN, COL_CLEAN};
+  int fused_read = -1, fused_col = 0, fused_mov = 0;  // buffer the last fused launch read: cleared by the next one (or clear_fused_read)
+};
+
 struct FastState {
   Rccl rccl;
   std::vector<RcclPeer> rpeers;
@@ -103,12 +192,10 @@ struct FastState {
   float mass_span = 1.0f;
   float global_mass_span = 0.0f;  // sharded runs: the span over ALL ranks' simulated particles (mpmhip_dist_set_mass_span); 0: not set
   bool p2g_fixed = true;       // p2g's chunk tile in packed fixed point (k_p2g<.., FX = true>); MPMHIP_P2G_TILE=f64: the fp64 tile
-  bool g2p_mflag = false;      // g2p asks m_flag before it loads a block's accumulators (one more dependent memory level at the head
-                               // of every workgroup; the default loads them with the particle positions): MPMHIP_G2P_MFLAG=1
   // adaptive collective re-sorts (mpmhip_rccl_steps with rebin_interval <= 0): the ranks' drift flags are max-reduced
   // every DIST_POLL substeps and read DIST_LAG substeps later, so every rank takes the same decision at the same substep
   int dist_since = 0;
-  bool dist_resort = false, dflag_pending = false, rccl_sorted = false;
+  bool dist_resort = false, dflag_in_flight = false, rccl_sorted = false;
   int64_t dflag_check_at = 0;
   unsigned dflag_seq = 0;  // sequence number of the last reduction posted to host memory (k_post_flag; wraps)
   std::vector<DistPeer> peers;
@@ -117,7 +204,6 @@ struct FastState {
   int blk_bits_plain = 0;          // bits of a block id (face-bin sort)
   float lead_steps = 12.0f;        // predictive sort: look this many substeps ahead (half the expected re-sort interval)
   float last_dt = 0.0f;
-  int poll_mask = 7;               // the drift flag is read back every poll_mask + 1 substeps (host lag <= twice that)
   int true_since_rebin = 0;        // substeps since the last re-sort (steps_since_rebin is overwritten to force one)
   size_t nblocks = 0;
   Bufs buf[2]{};
@@ -158,7 +244,7 @@ struct FastState {
   int *rcnt = nullptr; // device: counts of the last re-sort (RC_*)
   int64_t stat_steps = 0;
   int n_P = 0, n_A = 0, n_chunks = 0;
-  int *h_pin = nullptr;  // pinned host scratch
+  int *h_pin = nullptr;  // pinned host scratch, PIN_N ints (PIN_*)
   // host staging of the re-sort in pinned memory: device->host copies really are asynchronous, and the chunk table can
   // be uploaded without waiting for the copy (the next re-sort synchronises long before it touches the buffer again)
   template <class T>
@@ -189,8 +275,6 @@ struct FastState {
   bool elem_pending = false;  // element finalise of the last substep still to be done (fused into the next stress)
   bool all_simulated = false;      // no particle with selection != 0 (counted at every import with the mass span)
   int steps_since_rebin = 0;
-  hipEvent_t ev_flag = nullptr;
-  bool flag_pending = false;
   volatile int *h_sig = nullptr;  // pinned, host-mapped, written by the kernels (GridPtrs::host_sig)
   unsigned sig_seq = 0;           // step_id of the last p2g launch issued (wraps)
   unsigned sig_at_rebin = 0;      // sig_seq when the last re-sort finished: ring entries up to it speak about the old order
@@ -200,44 +284,28 @@ struct FastState {
   int64_t rebins = 0;
   int rebin_interval = 32;
   bool adaptive_rebin = true;
-  // fused grid stage: after a substep the accumulators of the active blocks are still loaded (g2p only read them);
-  // they are cleared by the next substep's stress launch (ZeroArgs) or, before a re-sort, by k_zero_blocks
-  bool fuse_grid = true, grid_dirty = false, fuse_trad = true;
-  int dirty_col = 0, dirty_mov = 0;
-  // A body AT REST inside one mpmhip_steps call (mesh_v == 0 for every vertex: checked once per call, fast_body_at_rest): its collider
-  // field -- weight, weight * velocity, weight * normal per node -- is the same in every substep, so it is splatted ONCE into each of
-  // the two accumulator buffers and then kept: no splat workgroups, no clearing of the collider channels, until the particle order
-  // (the face bins, the active list) changes or the call ends.  col_state[buffer]: 0 clean, 1 holds this substep's splat (cleared by
-  // the next launch's clearing workgroups, as ever), 2 holds the field of the body at rest (kept).
-  bool col_at_rest = false;      // this mpmhip_steps call's body does not move
-  int col_state[3] = {0, 0, 0};
+  // fused grid stage (no grid kernel: g2p evaluates the nodes, the accumulators stay loaded, see AccumRing); fused stress of
+  // the traditional particles (in front of p2g)
+  bool fuse_grid = true, fuse_trad = true;
+  AccumRing acc;
   int64_t n_col_kept = 0;        // substeps that ran without splat workgroups because the field was kept (statistics)
-  // accumulator double buffer: g.{mv,col,mov,m_flag,col_flag} point at buffer `par`
-  // (three for scenes that can run the fused g2p -> p2g launch, k_g2p2g: read / write / clear)
-  float *mv2[3] = {nullptr, nullptr, nullptr}, *col2[3] = {nullptr, nullptr, nullptr}, *mov2[3] = {nullptr, nullptr, nullptr};
-  int *mflag2[3] = {nullptr, nullptr, nullptr}, *cflag2[3] = {nullptr, nullptr, nullptr};
-  int par = 0, nbuf = 2;
-  // G2P2G: the g2p of the last substep has not been launched yet -- the next substep's launch does it in front of its own p2g
-  // (k_g2p2g), or flush_g2p() does with a plain k_g2p when anything else needs the particles first
   bool col_keep = true;        // MPMHIP_COL_KEEP=0: splat the body every substep whether it moves or not (A/B)
-  int *zero_flags = nullptr;   // [blocks] zeros (drop_kept_collider_fields)
   bool g2p2g = true;           // MPMHIP_G2P2G=0: two launches per substep for traditional-only scenes as before
   int g2p2g_max_chunks = 512;  // MPMHIP_G2P2G_MAX
   int stagger_auto = 2;        // p2g first-round stagger units for chunk lists of at least two rounds; -1: forced by MPMHIP_P2G_STAGGER
   int split_splat_max_chunks = 1024;  // MPMHIP_SPLIT_SPLAT_MAX
   bool split_splat = true;     // body-face splat: pass 0 in the stress launch, pass 1 in the p2g launch (MPMHIP_SPLIT_SPLAT=0: both in p2g)
   int64_t n_g2p2g = 0;         // fused launches so far (mpmhip_stats)
+  // G2P2G: the g2p of the last substep has not been launched yet -- the next substep's launch does it in front of its own p2g
+  // (k_g2p2g), or flush_g2p() does with a plain k_g2p when anything else needs the particles first
   bool g2p_pending = false;
   GridParams pend_gp{};
   BCList pend_bcl{};
   float pend_dt = 0.0f;
-  int clear_later = -1, cl_col = 0, cl_mov = 0;  // buffer the last fused launch read: cleared by the next one (or by flush_g2p)
-  GridParams last_gp{};
-  BCList last_bcl{};  // false: ignore the drift flag (tests of the out-of-margin paths)
+  GridParams last_gp{};  // grid-stage parameters of the last fused substep (materialize_grid)
+  BCList last_bcl{};
   std::vector<void *> allocs;
 };
-
-int flush_g2p(mpmhip_ctx *c);  // (defined with the step functions: launches the deferred g2p of a G2P2G sequence)
 
 
 template <class T>
@@ -269,18 +337,13 @@ inline void kstamp_launch(mpmhip_ctx *c, K kernel, unsigned grid, unsigned block
 int alloc_bufs(mpmhip_ctx *c, Bufs &b);
 int ensure_cap(mpmhip_ctx *c, int **p, int *cap, int need, int per);
 int scan_flags(mpmhip_ctx *c, const int *flag, int *index, int n, int *total);
-int scan_flags_dev(mpmhip_ctx *c, const int *flag, int *index, int n);
-int scan_flags_async(mpmhip_ctx *c, const int *flag, int *index, int n, int slot);
 int do_import(mpmhip_ctx *c);
 int rebin(mpmhip_ctx *c);
 // fast.hip
 int flush_elements(mpmhip_ctx *c);
-int flush_g2p(mpmhip_ctx *c);
-ZeroArgs take_zero(FastState *f);
-void select_buffer(FastState *f, int par);
-void flush_grid(mpmhip_ctx *c);
+int flush_g2p(mpmhip_ctx *c);  // launches the deferred g2p of a G2P2G sequence
+void launch_zero_blocks(hipStream_t s, const ZeroArgs &z);
 void materialize_grid(mpmhip_ctx *c, bool count);
-void drop_kept_collider_fields(mpmhip_ctx *c);
 int step_phase_a(mpmhip_ctx *c, const StepArgs &a);
 int step_phase_b(mpmhip_ctx *c, const StepArgs &a);
 int step_phase_c(mpmhip_ctx *c, const StepArgs &a);
@@ -289,8 +352,6 @@ void launch_p2g(mpmhip_ctx *c, bool trad, bool jt, unsigned grid, int n_chunks, 
 void launch_stress_elem(mpmhip_ctx *c, int mode, const SplatArgs &sa);
 void launch_stress_trad(mpmhip_ctx *c, float dt);
 void launch_g2p(mpmhip_ctx *c, bool fused, bool two, float dt, const GridParams &gp, const BCList &bcl);
-// api.hip
-void mesh_store_launch(mpmhip_ctx *c, const StepArgs &a);
 void launch_g2p2g(mpmhip_ctx *c, unsigned grid, float dt, const GridRead &rd, const SplatArgs &sa, const TradParams &tp, const GridParams &gp,
                   const BCList &bcl);
 

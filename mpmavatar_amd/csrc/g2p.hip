@@ -49,9 +49,6 @@ void launch_g2p(mpmhip_ctx *c, bool fused, bool two, float dt, const GridParams 
   } else if (f->g.halo.slot) {
     if (two) kstamp_launch(c, k_g2p_halo<true>, G2P_ARGS);
     else kstamp_launch(c, k_g2p_halo<false>, G2P_ARGS);
-  } else if (f->g2p_mflag) {
-    if (two) kstamp_launch(c, k_g2p<true, true, true, false>, G2P_ARGS);
-    else kstamp_launch(c, k_g2p<true, false, true, true>, G2P_ARGS);
   } else {
     if (two && wide) kstamp_launch(c, k_g2p<true, true, false, true>, G2P_ARGS);
     else if (two) kstamp_launch(c, k_g2p<true, true, false, false>, G2P_ARGS);

@@ -201,7 +201,7 @@ __device__ __forceinline__ G2PResult g2p_gather_global(V3 x, const Dims &d, cons
           const float *rem_mov = nullptr;
           int hs = g.halo.slot[blk];
           if (hs >= 0) {
-            link_wait_lane(halo_sig(g.halo, hs >> 24), g.halo.seq, g.counters + 10);
+            link_wait_lane(halo_sig(g.halo, hs >> 24), g.halo.seq, g.counters + CNT_LINK_TIMEOUT);
             rem_mov = halo_add_node(g.halo, hs, l_, m, px, py, pz);
           }
           u = node_finish<false>(blk, l_, m, px, py, pz, d, g, gp, bcl, nc, nm, true, 0xffffffffu, rem_mov);
@@ -346,7 +346,7 @@ __device__ __forceinline__ void g2p_body(const ChunkRec *recs, int n_chunks, con
           hs27 = g.halo.slot[(nx * d.NB + ny) * d.NB + nz];
       }
       for (int k = 0; k < g.halo.n_peers; ++k)
-        if (__any(hs27 >= 0 && (hs27 >> 24) == k)) link_wait(halo_sig(g.halo, k), g.halo.seq, g.counters + 10);
+        if (__any(hs27 >= 0 && (hs27 >> 24) == k)) link_wait(halo_sig(g.halo, k), g.halo.seq, g.counters + CNT_LINK_TIMEOUT);
     }
   }
   bool escaped = false;
@@ -427,7 +427,7 @@ __device__ __forceinline__ void g2p_body(const ChunkRec *recs, int n_chunks, con
     if (escaped) {
       G2PResult r = g2p_gather_global<FUSED, HALO>(x, d, g, gp, bcl);
       g2p_write(b, cls, s, x, d3, r, ox, oy, oz, d, dt, g);
-      atomicAdd(g.counters + 0, 1);
+      atomicAdd(g.counters + CNT_FALLBACK, 1);
     }
   }
   WGT(g, 1, 6);
@@ -569,7 +569,7 @@ __device__ __forceinline__ void g2p2g_body(const ChunkRec *recs, int n_chunks, c
     if (escaped) {
       G2PResult r = g2p_gather_global<true, false>(xe, d, gr, gp, bcl);
       g2p_write(b, 1, se, xe, v3(0, 0, 0), r, ox, oy, oz, d, dt, g);
-      atomicAdd(g.counters + 0, 1);
+      atomicAdd(g.counters + CNT_FALLBACK, 1);
       esc[atomicAdd(&esc_n, 1)] = (int)threadIdx.x | (1 << 16);
     }
   }

@@ -62,7 +62,7 @@ __device__ __forceinline__ void mover_splat_wg(const Bufs &b, const JointSplatAr
   float w = sel3(i, s.w0.x, s.w1.x, s.w2.x) * sel3(j, s.w0.y, s.w1.y, s.w2.y) * sel3(k, s.w0.z, s.w1.z, s.w2.z);
   int x = s.bx + i, y = s.by + j, z = s.bz + k;
   int blk = blk_of(x, y, z, d.NB);
-  if (!g.ab_flag[blk]) { atomicAdd(g.counters + 1, 1); return; }
+  if (!g.ab_flag[blk]) { atomicAdd(g.counters + CNT_DROPPED, 1); return; }
   V3 pv = load_v3(vel);
   float *p = g.mov + ((size_t)blk * GCH_MOV) * 64 + loc_of(x, y, z);
   atomicAdd(p, w);
@@ -378,7 +378,7 @@ template <bool TRAD>
 __device__ __forceinline__ void p2g_escaped(const Bufs &b, const VAdj &va, int cls, int s, const Dims &d, float rpic,
                                          float dt, GridPtrs g, const TradParams &tp) {
   P2GParticle q = p2g_load<TRAD>(b, va, cls, s, d, rpic, dt, tp);
-  atomicAdd(g.counters + 0, 1);
+  atomicAdd(g.counters + CNT_FALLBACK, 1);
 #pragma unroll 1
   for (int n = 0; n < 27; ++n) {
     int i = n / 9, j = (n / 3) % 3, k = n % 3;
@@ -388,7 +388,7 @@ __device__ __forceinline__ void p2g_escaped(const Bufs &b, const VAdj &va, int c
     int x = q.s.bx + i, y = q.s.by + j, z = q.s.bz + k;
     if (!in_grid(x, y, z, d.G)) continue;
     int blk = blk_of(x, y, z, d.NB);
-    if (!g.ab_flag[blk]) { atomicAdd(g.counters + 1, 1); continue; }
+    if (!g.ab_flag[blk]) { atomicAdd(g.counters + CNT_DROPPED, 1); continue; }
     float *p = g.mv + ((size_t)blk * GCH_MV) * 64 + loc_of(x, y, z);
     g.m_flag[blk] = 1;
     atomicAdd(p, wm);
@@ -422,7 +422,7 @@ __device__ __forceinline__ void p2g_scatter(double *tile, int *esc, int *esc_n_p
     if (DBG(g, 128)) do_add = false;
     if (DBG(g, 512)) {  // measurement: lanes that issue LDS atomics per lane that holds a particle
       unsigned long long ba = __ballot(do_add), bv = __ballot(valid);
-      if ((threadIdx.x & 63) == 0) { atomicAdd(g.counters + 8, __popcll(ba)); atomicAdd(g.counters + 9, __popcll(bv)); }
+      if ((threadIdx.x & 63) == 0) { atomicAdd(g.counters + CNT_EXP0, __popcll(ba)); atomicAdd(g.counters + CNT_EXP1, __popcll(bv)); }
     }
     const Stencil &st = q.s;
     // factored stencil: add_ijk = wz_k (wxym_ij (B_ij + k Cz) + P_ij) + dwz_k Q_ij,  wm = wxym_ij wz_k,  wxym = wx wy m
@@ -508,7 +508,7 @@ __device__ __forceinline__ void mover_escaped(V3 x, V3 pv, const Dims &d, const 
     float w = sel3(i, s.w0.x, s.w1.x, s.w2.x) * sel3(j, s.w0.y, s.w1.y, s.w2.y) * sel3(k, s.w0.z, s.w1.z, s.w2.z);
     int gx = s.bx + i, gy = s.by + j, gz = s.bz + k;
     int blk = blk_of(gx, gy, gz, d.NB);
-    if (!g.ab_flag[blk]) { atomicAdd(g.counters + 1, 1); continue; }
+    if (!g.ab_flag[blk]) { atomicAdd(g.counters + CNT_DROPPED, 1); continue; }
     float *p = g.mov + ((size_t)blk * GCH_MOV) * 64 + loc_of(gx, gy, gz);
     atomicAdd(p, w);
     atomicAdd(p + 64, w * pv.x); atomicAdd(p + 128, w * pv.y); atomicAdd(p + 192, w * pv.z);
@@ -890,7 +890,7 @@ __device__ __forceinline__ void p2g_body(const ChunkRec *recs, int n_chunks, con
   }
   if (bid >= sa.z_first) {  // ... and the clearing workgroups last: they fill the tail of the launch
     if (sa.pack.n_wg && bid >= sa.pack.first) {  // (multi-GPU) halo pack, once everything in front has scattered
-      pack_wait(sa.pack, g.counters + 10);
+      pack_wait(sa.pack, g.counters + CNT_LINK_TIMEOUT);
       halo_pack_wg<true>(sa.pack.tb, g, bid - sa.pack.first);
       return;
     }

@@ -547,38 +547,11 @@ int scan_flags(mpmhip_ctx *c, const int *flag, int *index, int n, int *total) {
     f->scan_tmp_bytes = need;
   }
   MPM_HIP_CHECK(c, rocprim::exclusive_scan(f->scan_tmp, need, flag, index, 0, (size_t)n, rocprim::plus<int>(), c->stream));
-  MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin, index + (n - 1), sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + 1, flag + (n - 1), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  int *h = f->h_pin + PIN_SCAN;  // (PIN_SCAN_N = 2 addends)
+  MPM_HIP_CHECK(c, hipMemcpyAsync(h, index + (n - 1), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  MPM_HIP_CHECK(c, hipMemcpyAsync(h + 1, flag + (n - 1), sizeof(int), hipMemcpyDeviceToHost, c->stream));
   MPM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-  *total = f->h_pin[0] + f->h_pin[1];
-  return MPMHIP_OK;
-}
-
-// the same scan without the wait: the two addends of the total land in h_pin[slot], h_pin[slot + 1] once the stream gets there
-int scan_flags_dev(mpmhip_ctx *c, const int *flag, int *index, int n) {  // exclusive scan, nothing read back
-  FastState *f = c->fast;
-  size_t need = 0;
-  MPM_HIP_CHECK(c, rocprim::exclusive_scan(nullptr, need, flag, index, 0, (size_t)n, rocprim::plus<int>(), c->stream));
-  if (need > f->scan_tmp_bytes) {
-    MPM_HIP_CHECK(c, hipMalloc(&f->scan_tmp, need));
-    f->allocs.push_back(f->scan_tmp);
-    f->scan_tmp_bytes = need;
-  }
-  MPM_HIP_CHECK(c, rocprim::exclusive_scan(f->scan_tmp, need, flag, index, 0, (size_t)n, rocprim::plus<int>(), c->stream));
-  return MPMHIP_OK;
-}
-int scan_flags_async(mpmhip_ctx *c, const int *flag, int *index, int n, int slot) {
-  FastState *f = c->fast;
-  size_t need = 0;
-  MPM_HIP_CHECK(c, rocprim::exclusive_scan(nullptr, need, flag, index, 0, (size_t)n, rocprim::plus<int>(), c->stream));
-  if (need > f->scan_tmp_bytes) {
-    MPM_HIP_CHECK(c, hipMalloc(&f->scan_tmp, need));
-    f->allocs.push_back(f->scan_tmp);
-    f->scan_tmp_bytes = need;
-  }
-  MPM_HIP_CHECK(c, rocprim::exclusive_scan(f->scan_tmp, need, flag, index, 0, (size_t)n, rocprim::plus<int>(), c->stream));
-  MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + slot, index + (n - 1), sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + slot + 1, flag + (n - 1), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  *total = h[0] + h[1];
   return MPMHIP_OK;
 }
 
@@ -605,9 +578,9 @@ int do_import(mpmhip_ctx *c) {
     MPM_HIP_CHECK(c, hipMemsetAsync(f->adj_cnt, 0, ((size_t)d.n_v + 1) * sizeof(int), s));
     hipLaunchKernelGGL(k_adj_build, nblk(d.n_e), TPB, 0, s, c->st.faces, d.n_e, d.n_v, f->adj_cnt, (int *)nullptr, 0, 0);
     hipLaunchKernelGGL(k_max_int, nblk(d.n_v), TPB, 0, s, f->adj_cnt, d.n_v, f->adj_cnt + d.n_v);
-    MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + 16, f->adj_cnt + d.n_v, sizeof(int), hipMemcpyDeviceToHost, s));
+    MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + PIN_ADJ_K, f->adj_cnt + d.n_v, sizeof(int), hipMemcpyDeviceToHost, s));
     MPM_HIP_CHECK(c, hipStreamSynchronize(s));
-    int K = std::max(f->h_pin[16], 1);
+    int K = std::max(f->h_pin[PIN_ADJ_K], 1);
     if (K > f->adj_cap) {
       int rc2;
       if ((rc2 = dalloc(c, &f->adj_o, (size_t)K * d.n_v, false))) return rc2;
@@ -692,15 +665,23 @@ int rebin(mpmhip_ctx *c) {
   hipStream_t s = c->stream;
   int cur = f->cur, alt = 1 - cur;
   int rc;
-  if (d.n_p == 0) { flush_grid(c); f->n_P = f->n_A = f->n_chunks = f->n_chunks_g = 0; f->steps_since_rebin = 0; return MPMHIP_OK; }
+  if (d.n_p == 0) {
+    const AccumRing::Relist relist = f->acc.begin_relist(s);
+    launch_zero_blocks(s, relist.z);
+    f->n_P = f->n_A = f->n_chunks = f->n_chunks_g = 0; f->steps_since_rebin = 0;
+    f->acc.end_relist(relist, f->alist, 0);
+    return MPMHIP_OK;
+  }
   flush_elements(c);
-  drop_kept_collider_fields(c);   // (a body at rest: its kept collider fields live on the OLD active list and in the old face bins)
+  // the active list and the face bins are about to change: kept collider fields go now, what the last substep left loaded is
+  // cleared by extra workgroups of k_keys (relist.z)
+  const AccumRing::Relist relist = f->acc.begin_relist(s);
   // k_keys: the keys (written where the sort wants its input, so that the sorted keys end up in keys[1] and the order in f->order),
   // the sort's first histogram, the zeroing of the block flags / counts, and -- as extra workgroups -- the clearing of the grid
-  // accumulators of the old active list (flush_grid)
+  // accumulators of the old active list
   const bool fused_hist = sort_custom(f, d.n_p);
   if (fused_hist && (rc = sort_reserve(c, d.n_p))) return rc;
-  const ZeroArgs z = take_zero(f);
+  const ZeroArgs &z = relist.z;
   const int key_tiles = (d.n_p + RS_TILE - 1) / RS_TILE;
   hipLaunchKernelGGL(k_keys, (unsigned)(key_tiles + z.n_wg), RS_TPB, 0, s, f->buf[cur], d, f->blk_bits, f->lead_steps * f->last_dt,
                      f->ghost_g2p ? 1 : 0, f->keys[sort_input(f, d.n_p, f->key_bits)], f->iota, f->pb_flag, f->n_clear,
@@ -719,9 +700,9 @@ int rebin(mpmhip_ctx *c) {
   const int nf = c->num_mesh_f;
   // The face bins survive a particle re-sort (they do not depend on the particle tables; only their compaction onto the
   // active list below does): the ~13 launches of the face sort run when a face has actually left its bin's tile since the
-  // last one (counters[5], seen through host memory), at the latest every 16th re-sort, and always in the sharded loops.
+  // last one (CNT_FACE, seen through host memory), at the latest every 16th re-sort, and always in the sharded loops.
   bool face_sort = with_faces;
-  if (with_faces && f->faces_binned && f->g.host_sig && !f->dist && !f->face_flag_seen && f->rebins_since_face_sort < 16 &&
+  if (with_faces && f->faces_binned && !f->dist && !f->face_flag_seen && f->rebins_since_face_sort < 16 &&
       !getenv("MPMHIP_FACE_SORT_ALWAYS"))
     face_sort = false;
   if (face_sort) {  // body faces: sort by block, per-block ranges (independent of the particle tables)
@@ -748,7 +729,6 @@ int rebin(mpmhip_ctx *c) {
     const int cap_A = (int)std::min<long long>((long long)nb, 27LL * cap_P);
     const int cap_ch = cap_P + d.n_p / CHUNK + 8;
     const int cap_fb = with_faces ? std::min(nf, cap_A + nf / PT + 1) : 0;   // (non-empty bins + the extra records of split bins)
-    int dummy = 0;
     if ((rc = ensure_cap(c, &f->plist, &f->alloc_P, cap_P, 1))) return rc;
     if ((rc = ensure_cap(c, &f->ranges, &f->cap_R, cap_P, 10))) return rc;
     if ((rc = ensure_cap(c, &f->alist, &f->cap_A, cap_A, 1))) return rc;
@@ -760,7 +740,6 @@ int rebin(mpmhip_ctx *c) {
       if ((rc = dalloc(c, &f->fbins, (size_t)cap_fb + 64, false))) return rc;
       f->cap_fbins = cap_fb + 64;
     }
-    (void)dummy;
     if (attempt > 0)  // (the first time k_keys has cleared them)
       MPM_HIP_CHECK(c, hipMemsetAsync(f->pb_flag, 0, (size_t)f->n_clear * sizeof(int), s));  // pb_flag, ab_flag, rcnt, fc_gsum
     if (attempt > 0 || !fused_hist) hipLaunchKernelGGL(k_mark_blocks, nblk(d.n_p), TPB, 0, s, skeys, d.n_p, f->blk_bits, f->pb_flag);
@@ -776,9 +755,9 @@ int rebin(mpmhip_ctx *c) {
     hipLaunchKernelGGL(k_build_chunks, 1, 1024, 0, s, f->plist, f->ranges, cap_P, f->rcnt, f->chunks, f->chunks + cap_ch, cap_ch, f->g.counters);
     if (with_faces)
       hipLaunchKernelGGL(k_fbin_compact, nblk(cap_A), TPB, 0, s, f->alist, f->rcnt, cap_A, f->fb_start, f->fb_cnt, f->fbins, cap_fb);
-    MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + 32, f->rcnt, RC_N * sizeof(int), hipMemcpyDeviceToHost, s));
+    MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + PIN_RCNT, f->rcnt, PIN_RCNT_N * sizeof(int), hipMemcpyDeviceToHost, s));
     if (f->mass_span_pending)
-      MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + 44, f->g.counters + CNT_MMIN, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+      MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + PIN_MASS, f->g.counters + CNT_MMIN, PIN_MASS_N * sizeof(int), hipMemcpyDeviceToHost, s));
     MPM_HIP_CHECK(c, hipStreamSynchronize(s));  // the one wait of a re-sort
     if (f->mass_span_pending) {
       // The fixed-point chunk tile gives every chunk ONE scale, from the sum of its lanes' bounds: a particle whose mass is
@@ -786,13 +765,14 @@ int rebin(mpmhip_ctx *c) {
       // sand 1e+6 times heavier v 1.1e-2 against 8.6e-5 with the fp64 tile; at 1e+4 both 2e-4).  Scenes whose particle masses
       // span more than 1e+5 therefore run the fp64 tile (MPMHIP_P2G_TILE=fx overrides).
       float lo, hi;
-      memcpy(&lo, f->h_pin + 44, 4); memcpy(&hi, f->h_pin + 45, 4);
+      const int *hm = f->h_pin + PIN_MASS;
+      memcpy(&lo, hm, 4); memcpy(&hi, hm + (CNT_MMAX - CNT_MMIN), 4);
       f->mass_span = (hi > 0.0f && lo < 3.0e38f) ? hi / lo : 1.0f;
       f->p2g_fixed_now = f->p2g_fixed && (f->p2g_fixed_forced || std::max(f->mass_span, f->global_mass_span) <= 1.0e5f);
-      f->all_simulated = f->h_pin[46] == 0;
+      f->all_simulated = hm[CNT_NSEL - CNT_MMIN] == 0;
       f->mass_span_pending = false;
     }
-    const int *h = f->h_pin + 32;
+    const int *h = f->h_pin + PIN_RCNT;
     if (h[RC_OVER]) {  // grow what was too small and build the tables again (the sorted particles stay as they are)
       f->cap_P = std::max(f->cap_P, std::min(nb, std::max(h[RC_NP], (h[RC_NCH] - d.n_p / CHUNK)) * 2 + 1024));
       if (h[RC_OVER] & ~1) f->cap_P = std::min(nb, f->cap_P * 2);
@@ -800,6 +780,7 @@ int rebin(mpmhip_ctx *c) {
     }
     f->n_P = h[RC_NP];
     f->n_A = h[RC_NA];
+    f->acc.end_relist(relist, f->alist, f->n_A);
     f->n_chunks = h[RC_NCH];
     const bool any_ghost = h[RC_GHOST] != 0;
     f->n_chunks_g = any_ghost ? h[RC_NCHG] : f->n_chunks;
@@ -822,8 +803,6 @@ int rebin(mpmhip_ctx *c) {
             (long)f->rebins, f->n_P, f->n_A, hc.size(), hist[0], hist[1], hist[2], hist[3], hist[4], f->lead_steps);
   }
   // (k_build_chunks has cleared the drift flag and the parity slots; ring entries up to sig_at_rebin are ignored anyway)
-  f->h_pin[24] = 0;
-  f->flag_pending = false;
   f->sig_at_rebin = f->sig_seq;  // ring entries of earlier substeps speak about the old order
   f->g.ab_flag = f->ab_flag;
   f->steps_since_rebin = 0;
