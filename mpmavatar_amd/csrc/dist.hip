@@ -119,9 +119,13 @@ __global__ void k_flags_to_bytes(const int *flag, int n, unsigned char *out) {
 
 
 // ---- multi-GPU entry points --------------------------------------------------------------------------------
+// a context becomes one rank of a sharded run (either transport): the drift look-ahead gets its multi-GPU default
+static void enter_dist_mode(FastState *f) {
+  f->dist = true;
+  if (!getenv("MPMHIP_DRIFT_LOOKAHEAD")) f->g.lookahead = DRIFT_LOOKAHEAD_DIST;
+}
 int fast_dist_enable(mpmhip_ctx *c) {
-  c->fast->dist = true;
-  if (!getenv("MPMHIP_DRIFT_LOOKAHEAD")) c->fast->g.lookahead = DRIFT_LOOKAHEAD_DIST;
+  enter_dist_mode(c->fast);
   return MPMHIP_OK;
 }
 int fast_dist_set_ghost_mode(mpmhip_ctx *c, int ghosts_gather) {
@@ -140,9 +144,9 @@ int fast_dist_set_mass_span(mpmhip_ctx *c, float min_mass, float max_mass) {
 }
 int fast_dist_num_blocks(const mpmhip_ctx *c) { return (int)c->fast->nblocks; }
 int64_t fast_dist_halo_bytes(const mpmhip_ctx *c) {  // bytes this rank sends per substep in the halo exchange (all peers)
-  int CH = c->movers.empty() ? 4 : 8;
+  int CH = halo_channels(!c->movers.empty());
   int64_t n = 0;
-  for (auto &p : c->fast->peers) n += (int64_t)p.n_blocks * CH * 64 * 4;
+  for (auto &p : c->fast->peers) n += (int64_t)(halo_floats(p.n_blocks, CH) * sizeof(float));
   return n;
 }
 
@@ -167,15 +171,7 @@ int fast_dist_set_peers(mpmhip_ctx *c, int n, const mpmhip_dist_peer *peers) {
   FastState *f = c->fast;
   if (n < 0 || n > 64 || (n > 0 && !peers)) return fail(c, MPMHIP_ERR_INVALID, "dist_set_peers: bad peer list");
   f->peers.clear();
-  for (int i = 0; i < n; ++i) {
-    const mpmhip_dist_peer &p = peers[i];
-    DistPeer q;
-    q.n_blocks = p.n_blocks; q.blocks = p.blocks; q.halo_send = p.halo_send; q.halo_recv = p.halo_recv;
-    q.n_send_p = p.n_send_p; q.n_recv_p = p.n_recv_p; q.n_send_e = p.n_send_e; q.n_recv_e = p.n_recv_e;
-    q.send_p = p.send_p; q.recv_p = p.recv_p; q.send_e = p.send_e; q.recv_e = p.recv_e;
-    q.ghost_send = p.ghost_send; q.ghost_recv = p.ghost_recv;
-    f->peers.push_back(q);
-  }
+  for (int i = 0; i < n; ++i) f->peers.push_back(DistPeer(peers[i]));
   return MPMHIP_OK;
 }
 
@@ -185,7 +181,7 @@ static inline bool peer_linked(const FastState *f, const DistPeer &p) {
 // halo (send = true: pack into halo_send, false: add halo_recv) for all peers, PEER_TAB per launch
 static void launch_halo(mpmhip_ctx *c, bool send) {
   FastState *f = c->fast;
-  int with_mov = c->movers.empty() ? 0 : 1, CH = with_mov ? 8 : 4;
+  int with_mov = c->movers.empty() ? 0 : 1, CH = halo_channels(with_mov);
   for (size_t i0 = 0; i0 < f->peers.size(); i0 += PEER_TAB) {
     HaloTab tb{};
     tb.with_mov = with_mov;
@@ -197,11 +193,11 @@ static void launch_halo(mpmhip_ctx *c, bool send) {
       if (peer_linked(f, p)) {  // store into / read from the receive arena of this pair instead, flag in the same memory
         float *arena = send ? p.link_remote : p.link_local;
         int par = (int)(f->halo_seq & 1u);
-        tb.buf[k] = arena + LINK_DATA0 + (size_t)par * p.link_cap * 8 * 64;
-        tb.sig[k] = (int *)arena + par * LINK_FLAG_STRIDE;
+        tb.buf[k] = link_data(arena, par, p.link_cap);
+        tb.sig[k] = link_flag(arena, par);
         tb.cnt[k] = p.link_cnt;
       }
-      tb.wg_off[k + 1] = tb.wg_off[k] + (int)nblk((size_t)p.n_blocks * CH * 64);
+      tb.wg_off[k + 1] = tb.wg_off[k] + (int)nblk(halo_floats(p.n_blocks, CH));
     }
     tb.seq = (int)f->halo_seq;
     if (!tb.n) continue;
@@ -251,13 +247,13 @@ int fast_dist_phase(mpmhip_ctx *c, int phase, const StepArgs &a) {
       h.slot = f->halo_slot;
       h.n_peers = (int)f->peers.size();
       h.seq = (int)f->halo_seq;
-      h.ch = c->movers.empty() ? 4 : 8;
+      h.ch = halo_channels(!c->movers.empty());
       const int par = (int)(f->halo_seq & 1u);
       for (size_t i = 0; i < f->peers.size(); ++i) {
         const DistPeer &q = f->peers[i];
         if (!q.n_blocks || !q.link_local) continue;
-        h.buf[i] = q.link_local + LINK_DATA0 + (size_t)par * q.link_cap * 8 * 64;
-        h.sig[i] = (const int *)q.link_local + par * LINK_FLAG_STRIDE;
+        h.buf[i] = link_data(q.link_local, par, q.link_cap);
+        h.sig[i] = link_flag(q.link_local, par);
       }
     }
     rc = step_phase_b(c, f->dist_args);
@@ -307,8 +303,7 @@ int fast_rccl_init(mpmhip_ctx *c, int rank, int world, const char id[128]) {
   MPM_NCCL_CHECK(c, f->rccl, f->rccl.CommInitRank(&f->rccl.comm, world, uid, rank));
   f->rccl.rank = rank;
   f->rccl.world = world;
-  f->dist = true;
-  if (!getenv("MPMHIP_DRIFT_LOOKAHEAD")) f->g.lookahead = DRIFT_LOOKAHEAD_DIST;
+  enter_dist_mode(f);
   const char *hm = getenv("MPMHIP_DIST_HALO");  // "rccl": keep the halos on ncclSend/ncclRecv; default: peer-mapped buffers
   f->link_want = !(hm && !strcmp(hm, "rccl"));
   int rc;
@@ -347,9 +342,20 @@ int fast_rccl_set_ghosts(mpmhip_ctx *c, int n, const int32_t *ranks, const int32
     if ((rc = up(&p->send_p, sp[i], nsp[i])) || (rc = up(&p->recv_p, rp[i], nrp[i])) || (rc = up(&p->send_e, se[i], nse[i])) ||
         (rc = up(&p->recv_e, re[i], nre[i])))
       return rc;
-    if ((rc = dalloc(c, &p->ghost_send, (size_t)6 * nsp[i] + 3 * nse[i] + 1))) return rc;
-    if ((rc = dalloc(c, &p->ghost_recv, (size_t)6 * nrp[i] + 3 * nre[i] + 1))) return rc;
+    if ((rc = dalloc(c, &p->ghost_send, ghost_floats(nsp[i], nse[i]) + 1))) return rc;
+    if ((rc = dalloc(c, &p->ghost_recv, ghost_floats(nrp[i], nre[i]) + 1))) return rc;
   }
+  return MPMHIP_OK;
+}
+
+// max over the ranks of CNT_LINK_VOTE (1: some link of this rank does not work), read back into h_pin[PIN_LINK_VOTE]
+static int reduce_vote(mpmhip_ctx *c) {
+  FastState *f = c->fast;
+  Rccl &r = f->rccl;
+  int *vote = f->g.counters + CNT_LINK_VOTE, *vote_all = f->g.counters + CNT_LINK_VOTE_ALL;
+  MPM_NCCL_CHECK(c, r, r.AllReduce(vote, vote_all, 1, ncclInt32, ncclMax, r.comm, c->stream));
+  MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + PIN_LINK_VOTE, vote_all, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  MPM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return MPMHIP_OK;
 }
 
@@ -374,7 +380,7 @@ static int rccl_link_setup(mpmhip_ctx *c) {
     if ((rc = dalloc(c, &p.link_cnt, 1))) return rc;
     if ((rc = dalloc(c, &p.hbuf, 256))) return rc;  // [0, 96): my IPC handle + PCI bus id, [128, 224): the peer's
     p.link_cap = std::max(4 * p.n_blocks, 1024);
-    size_t bytes = ((size_t)LINK_DATA0 + 2 * (size_t)p.link_cap * 8 * 64) * sizeof(float);
+    size_t bytes = link_arena_floats(p.link_cap) * sizeof(float);
     if (hipExtMallocWithFlags((void **)&p.link_local, bytes, hipDeviceMallocFinegrained) != hipSuccess) { p.link_local = nullptr; bad = 1; continue; }
     if (hipMemsetAsync(p.link_local, 0, bytes, s) != hipSuccess || hipIpcGetMemHandle(&mine[i], p.link_local) != hipSuccess) {
       memset(&mine[i], 0, sizeof(hipIpcMemHandle_t));
@@ -444,32 +450,26 @@ static int rccl_link_setup(mpmhip_ctx *c) {
   const char *fault = getenv("MPMHIP_LINK_FAULT");  // tests: this rank pretends its links failed
   if (fault && *fault && atoi(fault) == r.rank) bad = 1;
   // agree before the handshake: a rank without its links would leave its neighbours waiting for pings
-  int *vote = f->g.counters + CNT_LINK_VOTE, *vote_all = f->g.counters + CNT_LINK_VOTE_ALL;
-  MPM_HIP_CHECK(c, hipMemcpyAsync(vote, &bad, sizeof(int), hipMemcpyHostToDevice, s));
-  MPM_NCCL_CHECK(c, r, r.AllReduce(vote, vote_all, 1, ncclInt32, ncclMax, r.comm, s));
-  MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + PIN_LINK_VOTE, vote_all, sizeof(int), hipMemcpyDeviceToHost, s));
-  MPM_HIP_CHECK(c, hipStreamSynchronize(s));
+  MPM_HIP_CHECK(c, hipMemcpyAsync(f->g.counters + CNT_LINK_VOTE, &bad, sizeof(int), hipMemcpyHostToDevice, s));
+  if ((rc = reduce_vote(c))) return rc;
   if (f->h_pin[PIN_LINK_VOTE] == 0) {
     MPM_HIP_CHECK(c, hipMemsetAsync(f->g.counters + CNT_LINK_TIMEOUT, 0, 2 * sizeof(int), s));  // (TIMEOUT and BAD)
     for (int round = 0; round < 4; ++round) {
       int seq = (int)++f->halo_seq, par = seq & 1;
+      auto n_test = [](const RcclPeer &p) { return (int)std::min<size_t>(halo_floats(p.link_cap, HALO_CHANNELS_MAX), (size_t)1 << 16); };
       for (auto &p : f->rpeers) {
         if (!p.link_remote) continue;
-        int n = (int)std::min<size_t>((size_t)p.link_cap * 8 * 64, (size_t)1 << 16);
-        hipLaunchKernelGGL(k_link_ping, 16, TPB, 0, s, (unsigned *)p.link_remote + LINK_DATA0 + (size_t)par * p.link_cap * 8 * 64, n,
-                           p.link_cnt, (int *)p.link_remote + par * LINK_FLAG_STRIDE, seq);
+        hipLaunchKernelGGL(k_link_ping, 16, TPB, 0, s, (unsigned *)link_data(p.link_remote, par, p.link_cap), n_test(p), p.link_cnt,
+                           link_flag(p.link_remote, par), seq);
       }
       for (auto &p : f->rpeers) {
         if (!p.link_remote) continue;
-        int n = (int)std::min<size_t>((size_t)p.link_cap * 8 * 64, (size_t)1 << 16);
-        hipLaunchKernelGGL(k_link_check, 16, TPB, 0, s, (const unsigned *)p.link_local + LINK_DATA0 + (size_t)par * p.link_cap * 8 * 64, n,
-                           (const int *)p.link_local + par * LINK_FLAG_STRIDE, seq, f->g.counters);
+        hipLaunchKernelGGL(k_link_check, 16, TPB, 0, s, (const unsigned *)link_data(p.link_local, par, p.link_cap), n_test(p),
+                           (const int *)link_flag(p.link_local, par), seq, f->g.counters);
       }
     }
     hipLaunchKernelGGL(k_link_verdict, 1, 1, 0, s, f->g.counters);
-    MPM_NCCL_CHECK(c, r, r.AllReduce(vote, vote_all, 1, ncclInt32, ncclMax, r.comm, s));
-    MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + PIN_LINK_VOTE, vote_all, sizeof(int), hipMemcpyDeviceToHost, s));
-    MPM_HIP_CHECK(c, hipStreamSynchronize(s));
+    if ((rc = reduce_vote(c))) return rc;
     MPM_HIP_CHECK(c, hipMemsetAsync(f->g.counters + CNT_LINK_TIMEOUT, 0, 2 * sizeof(int), s));
   }
   f->link_on = f->h_pin[PIN_LINK_VOTE] == 0;
@@ -493,24 +493,14 @@ static int rccl_rebin(mpmhip_ctx *c) {
     if (p.n_blocks > p.cap_blocks) {
       int cap = std::max(p.n_blocks + p.n_blocks / 2, 256);
       if ((rc = dalloc(c, &p.blocks, (size_t)cap, false))) return rc;
-      if ((rc = dalloc(c, &p.halo_send, (size_t)cap * 8 * 64, false))) return rc;
-      if ((rc = dalloc(c, &p.halo_recv, (size_t)cap * 8 * 64, false))) return rc;
+      if ((rc = dalloc(c, &p.halo_send, halo_floats(cap, HALO_CHANNELS_MAX), false))) return rc;   // (sized for the wider record)
+      if ((rc = dalloc(c, &p.halo_recv, halo_floats(cap, HALO_CHANNELS_MAX), false))) return rc;
       p.cap_blocks = cap;
     }
     if (p.n_blocks) hipLaunchKernelGGL(k_compact, nblk(nb), TPB, 0, s, p.flag, p.index, nb, p.blocks, p.cap_blocks, (int *)nullptr, 0, 0, (int *)nullptr, 0);
-    DistPeer q;
-    q.n_blocks = p.n_blocks; q.blocks = p.blocks; q.halo_send = p.halo_send; q.halo_recv = p.halo_recv;
-    q.n_send_p = p.n_send_p; q.n_recv_p = p.n_recv_p; q.n_send_e = p.n_send_e; q.n_recv_e = p.n_recv_e;
-    q.send_p = p.send_p; q.recv_p = p.recv_p; q.send_e = p.send_e; q.recv_e = p.recv_e;
-    q.ghost_send = p.ghost_send; q.ghost_recv = p.ghost_recv;
-    f->peers.push_back(q);
   }
-  if (f->link_want && !f->link_decided && (rc = rccl_link_setup(c))) return rc;
-  for (size_t i = 0; i < f->peers.size(); ++i) {
-    const RcclPeer &p = f->rpeers[i];
-    DistPeer &q = f->peers[i];
-    q.link_local = p.link_local; q.link_remote = p.link_remote; q.link_cap = p.link_cap; q.link_cnt = p.link_cnt;
-  }
+  if (f->link_want && !f->link_decided && (rc = rccl_link_setup(c))) return rc;   // (first re-sort: the links come up here)
+  for (auto &p : f->rpeers) f->peers.push_back(p.view());
   // fused halo for this interval?
   f->fused_halo = false;
   if (f->fused_want && f->link_on && f->fuse_grid && f->peers.size() <= (size_t)PEER_TAB) {
@@ -539,14 +529,14 @@ static int rccl_rebin(mpmhip_ctx *c) {
 static int rccl_exchange(mpmhip_ctx *c, bool halo) {
   FastState *f = c->fast;
   Rccl &r = f->rccl;
-  int CH = c->movers.empty() ? 4 : 8;
+  int CH = halo_channels(!c->movers.empty());
   bool open = false;
   for (size_t i = 0; i < f->peers.size(); ++i) {
     const DistPeer &p = f->peers[i];
     int peer = f->rpeers[i].rank;
     if (halo && peer_linked(f, p)) continue;  // went through the pair's link (k_halo_pack / k_halo_add)
-    size_t ns = halo ? (size_t)p.n_blocks * CH * 64 : (size_t)6 * p.n_send_p + 3 * p.n_send_e;
-    size_t nr = halo ? (size_t)p.n_blocks * CH * 64 : (size_t)6 * p.n_recv_p + 3 * p.n_recv_e;
+    size_t ns = halo ? halo_floats(p.n_blocks, CH) : ghost_floats(p.n_send_p, p.n_send_e);
+    size_t nr = halo ? halo_floats(p.n_blocks, CH) : ghost_floats(p.n_recv_p, p.n_recv_e);
     if ((ns || nr) && !open) { MPM_NCCL_CHECK(c, r, r.GroupStart()); open = true; }
     if (ns) MPM_NCCL_CHECK(c, r, r.Send(halo ? p.halo_send : p.ghost_send, ns, ncclFloat, peer, r.comm, c->stream));
     if (nr) MPM_NCCL_CHECK(c, r, r.Recv(halo ? p.halo_recv : p.ghost_recv, nr, ncclFloat, peer, r.comm, c->stream));

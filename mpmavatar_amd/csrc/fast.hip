@@ -563,15 +563,15 @@ int step_phase_a(mpmhip_ctx *c, const StepArgs &a) {
   if (fused_halo_now) {  // (multi-GPU) the halo pack rides in this launch, behind the clearing workgroups: see PackArgs
     HaloTab &tb = sa.pack.tb;
     tb.with_mov = c->movers.empty() ? 0 : 1;
-    const int CH = tb.with_mov ? 8 : 4, par = (int)(f->halo_seq & 1u);
+    const int CH = halo_channels(tb.with_mov), par = (int)(f->halo_seq & 1u);
     for (auto &q : f->peers) {
       if (!q.n_blocks) continue;
       int k = tb.n++;
       tb.blocks[k] = q.blocks; tb.n_blocks[k] = q.n_blocks;
-      tb.buf[k] = q.link_remote + LINK_DATA0 + (size_t)par * q.link_cap * 8 * 64;
-      tb.sig[k] = (int *)q.link_remote + par * LINK_FLAG_STRIDE;
+      tb.buf[k] = link_data(q.link_remote, par, q.link_cap);
+      tb.sig[k] = link_flag(q.link_remote, par);
       tb.cnt[k] = q.link_cnt;
-      tb.wg_off[k + 1] = tb.wg_off[k] + (int)(((size_t)q.n_blocks * CH * 64 + PT - 1) / PT);
+      tb.wg_off[k + 1] = tb.wg_off[k] + (int)((halo_floats(q.n_blocks, CH) + PT - 1) / PT);
     }
     tb.seq = (int)f->halo_seq;
     sa.pack.n_wg = tb.wg_off[tb.n];

@@ -9,13 +9,9 @@ namespace mpm {
 // ================================================================================================
 // host side
 // ================================================================================================
-struct DistPeer {
-  int n_blocks = 0;
-  const int *blocks = nullptr;
-  float *halo_send = nullptr, *halo_recv = nullptr;
-  int n_send_p = 0, n_recv_p = 0, n_send_e = 0, n_recv_e = 0;
-  const int *send_p = nullptr, *recv_p = nullptr, *send_e = nullptr, *recv_e = nullptr;
-  float *ghost_send = nullptr, *ghost_recv = nullptr;
+struct DistPeer : mpmhip_dist_peer {  // the ABI's peer record (shared blocks, halo buffers, ghost lists) plus the pair's link
+  DistPeer() : mpmhip_dist_peer{} {}
+  explicit DistPeer(const mpmhip_dist_peer &p) : mpmhip_dist_peer(p) {}
   // peer link (in-library loop only): this rank's receive arena and the neighbour's, mapped; see rccl_link_setup
   float *link_local = nullptr, *link_remote = nullptr;
   int link_cap = 0;
@@ -76,8 +72,31 @@ struct RcclPeer {  // one neighbour rank: static ghost lists + per-re-sort share
   int link_cap = 0;
   int *link_cnt = nullptr;
   unsigned char *hbuf = nullptr;  // device staging of the two IPC handles (mine at 0, theirs at 64)
+
+  // what the substep's launches and the exchange use of this peer (FastState::peers), link fields included
+  DistPeer view() const {
+    DistPeer q;
+    q.n_blocks = n_blocks; q.blocks = blocks; q.halo_send = halo_send; q.halo_recv = halo_recv;
+    q.n_send_p = n_send_p; q.n_recv_p = n_recv_p; q.n_send_e = n_send_e; q.n_recv_e = n_recv_e;
+    q.send_p = send_p; q.recv_p = recv_p; q.send_e = send_e; q.recv_e = recv_e;
+    q.ghost_send = ghost_send; q.ghost_recv = ghost_recv;
+    q.link_local = link_local; q.link_remote = link_remote; q.link_cap = link_cap; q.link_cnt = link_cnt;
+    return q;
+  }
 };
+
+// Record sizes of the two exchanges, in floats (mpmavatar_amd/dist.py has the same two functions; include/mpmhip.h states them
+// at mpmhip_dist_peer).  Halo: 64 nodes per channel of a shared block, (m, momentum) = 4 channels, 8 with a particle mover.
+// Ghosts: x, v of a vertex / traditional particle, the director d3 of an element.
+constexpr int HALO_CHANNELS_MAX = 8;  // the in-library loop sizes its halo buffers and link arenas for the wider record
+inline int halo_channels(bool movers) { return movers ? 8 : 4; }
+constexpr size_t halo_floats(size_t n_blocks, int channels) { return n_blocks * (size_t)channels * 64; }
+constexpr size_t ghost_floats(size_t n_p, size_t n_e) { return 6 * n_p + 3 * n_e; }
+// the peer-link arena (layout at RcclPeer): where parity `par`'s data and flag sit
 constexpr int LINK_DATA0 = 32, LINK_FLAG_STRIDE = 16;
+constexpr size_t link_arena_floats(int cap) { return (size_t)LINK_DATA0 + 2 * halo_floats((size_t)cap, HALO_CHANNELS_MAX); }
+inline float *link_data(float *arena, int par, int cap) { return arena + LINK_DATA0 + (size_t)par * halo_floats((size_t)cap, HALO_CHANNELS_MAX); }
+inline int *link_flag(float *arena, int par) { return (int *)arena + par * LINK_FLAG_STRIDE; }
 
 // Pinned host scratch (FastState::h_pin): where the read-backs behind the host's waits land.  One name per slot; a block is
 // [first, first + its _N).  The slots are laid out one after the other, so no two can share a word; the assert keeps that true

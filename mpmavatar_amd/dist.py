@@ -34,11 +34,18 @@ path can be exercised with two processes on one GPU (tests/test_gpu_dist.py) and
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass, field, replace
+import os
+import sys
+import time
+from dataclasses import dataclass, field, fields, replace
 from typing import Dict, List
 
 import numpy as np
+import torch
+import torch.distributed as dist
 
+from . import _lib as L
+from . import harness
 from .scenes import Scene
 
 
@@ -62,6 +69,52 @@ class Shard:
     t_gid: np.ndarray = None          # local traditional row -> global traditional id, -1 = free row (slack for on-device migration);
                                       # free rows first, owned rows behind them in ascending id order (own_t = t_gid[t_gid >= 0])
 
+    # The row layout of the local scene, i.e. of every per-particle tensor of this rank's solver -- the contract with partition():
+    #   elements      [0, n_el):           own_e, then ghost_e
+    #   traditional   trad_rows:           one row per entry of t_gid (free rows included)
+    #   vertices      from trad_rows.stop: own_v (own_vertex_rows), then ghost_v
+    @property
+    def n_el(self) -> int:
+        return self.own_e.size + self.ghost_e.size
+
+    @property
+    def trad_rows(self) -> slice:
+        return slice(self.n_el, self.n_el + self.t_gid.size)
+
+    @property
+    def own_trad(self) -> np.ndarray:
+        """The owned rows of the traditional class, as indices INTO trad_rows (ascending global id)."""
+        return np.nonzero(self.t_gid >= 0)[0]
+
+    @property
+    def own_vertex_rows(self) -> slice:
+        v0 = self.trad_rows.stop
+        return slice(v0, v0 + self.own_v.size)
+
+    def owned_rows(self, sc: Scene):
+        """Global particle index of every OWNED local particle, and the local rows they sit in: (rows_local, ids_global) for the
+        all-particle arrays (x, v, C, model arrays) and for the element+traditional ones (F, F_trial, stress).  sc: the unsharded
+        scene."""
+        ne_g, nt_g = sc.n_elements, sc.n_traditional
+        t_loc = self.own_trad
+        rows_e = np.arange(self.own_e.size)
+        rows_t = self.trad_rows.start + t_loc
+        rows_v = np.arange(self.own_vertex_rows.start, self.own_vertex_rows.stop)
+        all_rows = np.concatenate([rows_e, rows_t, rows_v])
+        all_ids = np.concatenate([self.own_e, ne_g + self.t_gid[t_loc], ne_g + nt_g + self.own_v])
+        nv_rows = np.concatenate([rows_e, rows_t])
+        nv_ids = np.concatenate([self.own_e, ne_g + self.t_gid[t_loc]])
+        return all_rows, all_ids, nv_rows, nv_ids
+
+    def local_ids(self, sc: Scene):
+        """Global particle index of EVERY local row, ghosts included (a free row: some valid particle's): (all-particle arrays,
+        element+traditional arrays)."""
+        el = np.concatenate([self.own_e, self.ghost_e])
+        vl = np.concatenate([self.own_v, self.ghost_v])
+        t_ids = np.where(self.t_gid >= 0, self.t_gid, self.own_t[0] if self.own_t.size else 0)
+        nv_ids = np.concatenate([el, sc.n_elements + t_ids])
+        return np.concatenate([nv_ids, sc.n_elements + sc.n_traditional + vl]), nv_ids
+
 
 _TEST_FAIL_BUILD_RANK = None   # test hook (tests/dist_worker.py sets it): the rank whose local build raises; never read from the environment
 
@@ -72,6 +125,45 @@ TRAD_SLACK, TRAD_SLACK_MIN = 0.25, 256
 
 
 CUT_BINS = 1 << 14   # histogram resolution of the device-side quantile cut: grid_lim / 16384 (1/64 cell at 256^3)
+
+
+# Record sizes of the two exchanges, in floats (csrc/fast_state.hpp has the same two functions; include/mpmhip.h states them at
+# mpmhip_dist_peer).  Halo: 64 nodes per channel of a shared block.  Ghosts: x, v of a vertex, the director d3 of an element.
+def halo_channels(movers) -> int:
+    return 8 if movers else 4      # (m, momentum), and the mover's four with a particle mover
+
+
+def halo_floats(n_blocks: int, channels: int) -> int:
+    return n_blocks * channels * 64
+
+
+def ghost_floats(n_p: int, n_e: int) -> int:
+    return 6 * n_p + 3 * n_e
+
+
+# --------------------------------------------------------------------------------------------- collectives
+# The two places that know what a backend wants: gloo takes host tensors, nccl (= RCCL) device tensors.  (Collectives run at world
+# size 1 too: a tensor on the wrong device for the backend -- NCCL takes no CPU tensors -- then fails on a one-GPU test box and not
+# first on the node.)
+def _wire(backend: str, device):
+    return torch.device("cpu") if backend == "gloo" else torch.device(device)
+
+
+def _all_reduce(backend: str, device, values, op=dist.ReduceOp.SUM, dtype=torch.int32):
+    """ONE all-reduce.  values: a list of Python numbers (made a `dtype` tensor where the backend wants it; returns the reduced
+    numbers as a list) or a tensor (taken there as it is; returns the reduced tensor)."""
+    numbers = not torch.is_tensor(values)
+    t = torch.tensor(values, dtype=dtype, device=_wire(backend, device)) if numbers else values.to(_wire(backend, device))
+    dist.all_reduce(t, op=op)
+    return t.tolist() if numbers else t
+
+
+def _all_gather(backend: str, t, world: int):
+    """ONE all-gather of a device tensor of the same shape on every rank: the world tensors, where the backend left them."""
+    t = t.to(_wire(backend, t.device))
+    outs = [torch.zeros_like(t) for _ in range(world)]
+    dist.all_gather(outs, t)
+    return outs
 
 
 def cuts_from_histogram(hist, world: int, grid_lim: float) -> np.ndarray:
@@ -88,34 +180,30 @@ def cuts_from_histogram(hist, world: int, grid_lim: float) -> np.ndarray:
     return (idx + 1).astype(np.float64) * (float(grid_lim) / h.size)
 
 
+def slab_histogram(xs, grid_lim: float):
+    """This rank's addend of device_cuts(): CUT_BINS int64 counts of xs (a tensor of x coordinates, possibly empty: a rank that owns
+    nothing contributes zeros) over [0, grid_lim), on xs.device."""
+    if xs.numel() == 0:
+        return torch.zeros(CUT_BINS, dtype=torch.int64, device=xs.device)
+    return torch.histc(xs.float(), bins=CUT_BINS, min=0.0, max=float(grid_lim)).to(torch.int64)
+
+
 def device_cuts(ss: "ShardedSim") -> np.ndarray:
     """Collective: new slab boundaries at the particles' CURRENT positions without bringing a position to the host: every rank
     histograms the x of the particles it owns on its GPU (torch.histc), the histograms are summed over the ranks (one all-reduce of
-    64 KiB) and every rank reads the same cuts off the same cumulative counts.  (Round 3: np.quantile over the all-gathered
+    128 KiB) and every rank reads the same cuts off the same cumulative counts.  (Round 3: np.quantile over the all-gathered
     positions of the whole scene.)"""
-    import torch
-    import torch.distributed as dist
-    sh = ss.shard
-    xs = _owned_movable_x(ss).float()
     lim = float(ss.global_scene.grid_lim)
-    h = torch.histc(xs, bins=CUT_BINS, min=0.0, max=lim) if xs.numel() else torch.zeros(CUT_BINS, device=x.device)
-    h = h.to(torch.int64)
-    h = h.cpu() if ss.backend == "gloo" else h
-    dist.all_reduce(h)
-    return cuts_from_histogram(h.cpu().numpy(), sh.world, lim)
+    h = _all_reduce(ss.backend, ss.device, slab_histogram(owned_movable_x(ss.shard, ss.sim.state.particle_x.detach()), lim))
+    return cuts_from_histogram(h.cpu().numpy(), ss.shard.world, lim)
 
 
-def _owned_movable_x(ss: "ShardedSim"):
-    """x of the traditional particles and vertices this rank OWNS (device tensor): traditional rows by their global-id table (free
-    rows of the migration slack excluded), then the owned vertices (the first own_v rows of the vertex class)."""
-    import torch
-    sh = ss.shard
-    x = ss.sim.state.particle_x.detach()[:, 0]
-    ne_l = sh.own_e.size + sh.ghost_e.size
-    nt_l = sh.t_gid.size
-    own_rows = torch.as_tensor(np.nonzero(sh.t_gid >= 0)[0], device=x.device, dtype=torch.int64)
-    xt = x[ne_l:ne_l + nt_l][own_rows] if nt_l else x[:0]
-    return torch.cat([xt, x[ne_l + nt_l:ne_l + nt_l + sh.own_v.size]])
+def owned_movable_x(sh: Shard, particle_x):
+    """x of the traditional particles and vertices a rank OWNS, out of its [local rows, 3] position tensor: traditional rows by their
+    global-id table (free rows of the migration slack excluded), then the owned vertices."""
+    x = particle_x[:, 0]
+    own_rows = torch.as_tensor(sh.own_trad, device=x.device, dtype=torch.int64)
+    return torch.cat([x[sh.trad_rows][own_rows], x[sh.own_vertex_rows]])
 
 
 def _owners(sc: Scene, world: int, cuts=None):
@@ -196,41 +284,105 @@ def partition(sc: Scene, world: int, cuts=None, slack: bool = True) -> List[Shar
     return shards
 
 
+
+
 # --------------------------------------------------------------------------------------------- runtime
 @dataclass
-class ShardedSim:
+class GhostLists:
+    """The static ghost exchange with one peer (device tensors, alive as long as the partition): caller-order particle / element
+    indices to pack from and unpack into, and the two record buffers."""
+    send_p: torch.Tensor
+    recv_p: torch.Tensor
+    send_e: torch.Tensor
+    recv_e: torch.Tensor
+    gs: torch.Tensor
+    gr: torch.Tensor
+
+    @property
+    def n_send(self) -> int:
+        return ghost_floats(self.send_p.numel(), self.send_e.numel())
+
+    @property
+    def n_recv(self) -> int:
+        return ghost_floats(self.recv_p.numel(), self.recv_e.numel())
+
+
+@dataclass
+class StaticBuffers:
+    """What a rank hands the library once per partition: its active-block map and the ghost lists per peer."""
+    block_map: torch.Tensor
+    ghosts: Dict[int, GhostLists]
+
+    def __len__(self):   # (bench.py reports len(ss.static) - 1 as the number of peers with ghost lists)
+        return 1 + len(self.ghosts)
+
+
+@dataclass
+class Peer:
+    """One neighbour of the Python-driven transport between two collective re-sorts: the blocks both ranks have on their active
+    lists and the halo buffers for them (the library holds their addresses: they live here), the ghost lists if there are any."""
+    rank: int
+    blocks: torch.Tensor
+    hs: torch.Tensor
+    hr: torch.Tensor
+    n_halo: int
+    ghosts: GhostLists = None
+
+
+@dataclass
+class BodyPose:
+    """The body of one frame of a scene posed per frame, as the substep calls take it (see _body_at)."""
+    frame: int
+    tensors: tuple
+
+
+@dataclass
+class PartitionState:
+    """What belongs to ONE partition: build_sharded() makes it, repartition() replaces all of it by the fresh build's."""
     shard: Shard
     sim: object                        # harness.Sim of the local scene
     backend: str
     rebin_interval: int
+    device: torch.device = None
     transport: str = "torch"           # "rccl": loop inside libmpmhip.so; "torch": phases driven from Python
     ghost_g2p: bool = True             # ghost copies gather for themselves (one exchange per substep)
-    steps_done: int = 0
     since: int = 0                     # substeps since the last collective re-sort
     resort_now: bool = False           # some rank's drift flag was up at the last poll
     sorted_once: bool = False
-    resorts: int = 0
-    peers: list = field(default_factory=list)
-    keep: list = field(default_factory=list)
-    static: dict = field(default_factory=dict)
+    peers: List[Peer] = field(default_factory=list)
+    static: StaticBuffers = None
     global_scene: Scene = None         # the unsharded scene this shard was cut from (positions as of the last partition)
+    halo_ref: int = 0                  # max over the ranks of the halo bytes per substep right after the partition's first re-sort
+    mass_version: tuple = ()           # (data_ptr, version counter) of state.particle_mass when the ranks last agreed on the scene's mass span
+    body_pose: BodyPose = None         # the pose the last substep call used; its tensors stay alive until the next frame's replace them
+    held_buf: torch.Tensor = None      # joint_traditional_v of the staged release (zeros, one row per local traditional row)
+    migrate_warned: bool = False       # (said once per partition)
+
+
+@dataclass
+class RunState:
+    """What a re-partition leaves alone: the policy knobs a caller sets and the counters of the whole run."""
+    steps_done: int = 0
+    resorts: int = 0
     migrate_fraction: float = 0.10     # re-partition when more than this fraction of the particles left their slab (0: never) ...
     migrate_halo_factor: float = 1.5   # ... AND the halo -- the bytes a rank sends per substep -- has grown by this factor since the
                                        # partition was cut (0: do not ask).  A body that MOVES keeps its halo: a garment walking across
                                        # the slabs, a cube thrown along x leave "their" slabs entirely without a single block more to
                                        # exchange, and ownership is a matter of performance only (any two ranks exchange whatever blocks
                                        # they share); only material that MIXES across the cut (poured sand) makes the halo grow
-    halo_ref: int = 0                  # max over the ranks of the halo bytes per substep right after the partition's first re-sort
     migrate_check_every: int = 512     # ... looked at every this many substeps (one device-side count + one all-reduce)
     migrate_checked_at: int = 0
-    migrate_warned: bool = False
     migrations: int = 0
     migrate_trad_fraction: float = 0.01   # on-device migration of traditional particles when at least this fraction of them lies in
                                           # another rank's slab of the CURRENT quantile cuts (0: at every check; < 0: never)
     trad_migrations: int = 0              # on-device migration events / particles moved by them / wall time spent in them
     trad_migrated: int = 0
     trad_migration_ms: list = field(default_factory=list)   # wall time of every event (the first pays torch's one-time kernel loads)
-    mass_version: tuple = ()           # (data_ptr, version counter) of state.particle_mass when the ranks last agreed on the scene's mass span
+
+
+@dataclass
+class ShardedSim(RunState, PartitionState):
+    """One rank of a sharded simulation.  Every attribute is a field of one of the two groups above."""
 
 
 def sync_mass_span(ss: "ShardedSim") -> float:
@@ -240,8 +392,6 @@ def sync_mass_span(ss: "ShardedSim") -> float:
     WHOLE scene exceeds 1e5 -- a rank deciding from its own shard could run other accumulator numerics than its neighbour on the halo
     blocks they share, and a decision taken from the scene description would miss masses changed after the build.
     Returns the span."""
-    import torch
-    import torch.distributed as dist
     st, sv = ss.sim.state, ss.sim.solver
     mt = st._raw("particle_mass")
     m = mt.detach().float().reshape(-1)
@@ -253,9 +403,8 @@ def sync_mass_span(ss: "ShardedSim") -> float:
     lo = torch.where(ok, m, torch.full_like(m, big)).min() if m.numel() else torch.tensor(big, device=m.device)
     hi = torch.where(ok, m, torch.zeros_like(m)).max() if m.numel() else torch.tensor(0.0, device=m.device)
     t = torch.stack([-lo, hi]).to(torch.float32)      # one MAX all-reduce: max(-lo) = -min(lo)
-    t = t.cpu() if ss.backend == "gloo" else t
-    dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    lo_g, hi_g = -float(t[0].item()), float(t[1].item())
+    neg_lo, hi_g = _all_reduce(ss.backend, ss.device, t, op=dist.ReduceOp.MAX).tolist()
+    lo_g = -neg_lo
     if hi_g <= 0.0 or lo_g >= big:
         lo_g, hi_g = 0.0, 0.0                           # no simulated particle anywhere
     sv._call("mpmhip_dist_set_mass_span", float(lo_g), float(hi_g))
@@ -266,10 +415,6 @@ def sync_mass_span(ss: "ShardedSim") -> float:
 def build_sharded(sc: Scene, device, rank: int, world: int, rebin_interval: int = 0, _carry: dict = None, _cuts=None) -> ShardedSim:
     """Collective.  ``_carry`` / ``_cuts`` (re-partition only): per-particle state in GLOBAL order to continue from and the slab
     boundaries to cut at, see repartition()."""
-    import os
-    import torch
-    import torch.distributed as dist
-    from . import harness
     dev = torch.device(device)
     backend = dist.get_backend()
     # (1) Everything that can fail on ONE rank alone -- host memory for the partition, device memory for the solver and the exchange
@@ -291,26 +436,20 @@ def build_sharded(sc: Scene, device, rank: int, world: int, rebin_interval: int 
         sv._call("mpmhip_dist_enable")
         ghost_g2p = os.environ.get("MPMHIP_DIST_GHOST_G2P", "1") != "0"
         sv._call("mpmhip_dist_set_ghost_mode", 1 if ghost_g2p else 0)
-        ss = ShardedSim(shard, sim, backend, int(rebin_interval), ghost_g2p=ghost_g2p)
-        ss.global_scene = sc
+        ss = ShardedSim(shard, sim, backend, int(rebin_interval), device=dev, ghost_g2p=ghost_g2p, global_scene=sc)
         i32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.int32), device=dev)
+        buf = lambda n: torch.zeros(max(n, 1), dtype=torch.float32, device=dev)
+        ghosts = {}
         for q in sorted(set(shard.send_p) | set(shard.recv_p)):
-            ss.static[q] = dict(send_p=i32(shard.send_p[q]), recv_p=i32(shard.recv_p[q]), send_e=i32(shard.send_e[q]),
-                                recv_e=i32(shard.recv_e[q]))
-            n_s = 6 * len(shard.send_p[q]) + 3 * len(shard.send_e[q])
-            n_r = 6 * len(shard.recv_p[q]) + 3 * len(shard.recv_e[q])
-            ss.static[q]["gs"] = torch.zeros(max(n_s, 1), dtype=torch.float32, device=dev)
-            ss.static[q]["gr"] = torch.zeros(max(n_r, 1), dtype=torch.float32, device=dev)
+            g = GhostLists(i32(shard.send_p[q]), i32(shard.recv_p[q]), i32(shard.send_e[q]), i32(shard.recv_e[q]), None, None)
+            g.gs, g.gr = buf(g.n_send), buf(g.n_recv)
+            ghosts[q] = g
         nb = sv._lib.mpmhip_dist_num_blocks(sv._ctx)
-        ss.static["map"] = torch.zeros(nb, dtype=torch.uint8, device=dev)
+        ss.static = StaticBuffers(torch.zeros(nb, dtype=torch.uint8, device=dev), ghosts)
     except Exception as e:  # noqa: BLE001 - reported collectively right below
         err = e
     if world > 1:
-        ok = torch.tensor([0 if err is not None else 1], dtype=torch.int32)
-        if backend == "nccl":
-            ok = ok.to(dev)
-        dist.all_reduce(ok, op=dist.ReduceOp.MIN)
-        if int(ok.item()) != 1:
+        if _all_reduce(backend, dev, [0 if err is not None else 1], op=dist.ReduceOp.MIN) != [1]:
             if ss is not None:
                 ss.sim.solver.close()
             raise RuntimeError("mpmavatar_amd.dist.build_sharded: the local part of the build failed on "
@@ -327,69 +466,46 @@ def build_sharded(sc: Scene, device, rank: int, world: int, rebin_interval: int 
         except Exception as e:  # noqa: BLE001 - any failure means "use the torch transport"
             print(f"[mpmavatar_amd.dist] rank {rank}: in-library RCCL transport unavailable ({e}); using torch.distributed", flush=True)
             ok = 0
-        flag = torch.tensor([ok], dtype=torch.int32, device=dev if ss.backend == "nccl" else "cpu")
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        ss.transport = "rccl" if int(flag.item()) == 1 else "torch"
+        ss.transport = "rccl" if _all_reduce(backend, dev, [ok], op=dist.ReduceOp.MIN) == [1] else "torch"
     sync_mass_span(ss)
     return ss
 
 
 # --------------------------------------------------------------------------------------------- migration
-# per-particle state a re-partition carries over (particle_mass: reset_density(update_mass=True) after the initial build;
-# mu / lam / yield_stress below: set_E_nu* / prepare_mu_lam after the build and the plastic history).  NOT carried: edits of
-# particle_selection made after build_sharded, and the host-side state of grid BCs (a moving velocity cuboid's position) --
-# scenes with such a BC are not re-partitioned (maybe_repartition warns once and goes on).
-_CARRY_FIELDS = ("particle_x", "particle_v", "particle_C", "particle_d", "particle_F", "particle_F_trial", "particle_stress",
-                 "particle_mass")
-_CARRY_MODEL = ("mu", "lam", "yield_stress")
-
-
-def local_to_global_rows(shard: Shard, sc: Scene):
-    """Global particle index of every OWNED local particle, and the local rows they sit in: (rows_local, ids_global) for the
-    all-particle arrays (x, v, C, model arrays) and for the element+traditional ones (F, F_trial, stress)."""
-    ne_g, nt_g = sc.n_elements, sc.n_traditional
-    ne_l = shard.own_e.size + shard.ghost_e.size
-    nt_l = shard.t_gid.size                                  # local traditional rows incl. free ones
-    t_loc = np.nonzero(shard.t_gid >= 0)[0]                  # ... the owned ones among them
-    rows_e = np.arange(shard.own_e.size)
-    rows_t = ne_l + t_loc
-    rows_v = ne_l + nt_l + np.arange(shard.own_v.size)
-    all_rows = np.concatenate([rows_e, rows_t, rows_v])
-    all_ids = np.concatenate([shard.own_e, ne_g + shard.t_gid[t_loc], ne_g + nt_g + shard.own_v])
-    nv_rows = np.concatenate([rows_e, rows_t])
-    nv_ids = np.concatenate([shard.own_e, ne_g + shard.t_gid[t_loc]])
-    return all_rows, all_ids, nv_rows, nv_ids
+# Per-particle state a re-partition carries over: field -> (where it lives, the id set it is indexed by: "all" every particle, "nv"
+# elements + traditional, "e" elements).  (particle_mass: reset_density(update_mass=True) after the initial build; mu / lam /
+# yield_stress: set_E_nu* / prepare_mu_lam after the build and the plastic history.)  NOT carried: edits of particle_selection
+# made after build_sharded, and the host-side state of grid BCs (a moving velocity cuboid's position) -- scenes with such a BC are
+# not re-partitioned (maybe_repartition warns once and goes on).
+CARRIED = {"particle_x": ("state", "all"), "particle_v": ("state", "all"), "particle_C": ("state", "all"), "particle_d": ("state", "e"),
+           "particle_F": ("state", "nv"), "particle_F_trial": ("state", "nv"), "particle_stress": ("state", "nv"),
+           "particle_mass": ("state", "all"), "mu": ("model", "all"), "lam": ("model", "all"), "yield_stress": ("model", "all")}
+_CARRIED_BY_THE_SCENE = ("particle_x", "particle_v", "particle_d")   # repartition() puts them into the Scene the new shards are cut from
 
 
 def owned_slices(local: dict, shard: Shard, sc: Scene) -> dict:
     """The rows of a rank's local arrays (local particle order) that belong to particles it OWNS, with their global ids."""
-    all_rows, all_ids, nv_rows, nv_ids = local_to_global_rows(shard, sc)
-    n_loc = shard.scene.n_particles
+    all_rows, all_ids, nv_rows, nv_ids = shard.owned_rows(sc)
+    rows = {"all": all_rows, "nv": nv_rows, "e": np.arange(shard.own_e.size)}
     out = {"all_ids": all_ids, "nv_ids": nv_ids, "e_ids": shard.own_e}
     for f, a in local.items():
-        if f == "particle_d":
-            out[f] = a[:shard.own_e.size]
-        elif f in _CARRY_MODEL or f in ("particle_x", "particle_v", "particle_C", "particle_mass"):
-            assert a.shape[0] == n_loc, (f, a.shape, n_loc)
-            out[f] = a[all_rows]
-        else:
-            out[f] = a[nv_rows]
+        cls = CARRIED[f][1]
+        assert cls != "all" or a.shape[0] == shard.scene.n_particles, (f, a.shape, shard.scene.n_particles)
+        out[f] = a[rows[cls]]
     return out
 
 
 def assemble_global(parts, sc: Scene) -> dict:
     """Per-rank owned slices -> arrays in the global (unsharded) particle order."""
-    n_p, n_nv, n_e = sc.n_particles, sc.n_elements + sc.n_traditional, sc.n_elements
+    size = {"all": sc.n_particles, "nv": sc.n_elements + sc.n_traditional, "e": sc.n_elements}
     out = {}
-    for f in _CARRY_FIELDS + _CARRY_MODEL:
+    for f, (_, cls) in CARRIED.items():
         if f not in parts[0]:
             continue
-        whole = f in _CARRY_MODEL or f in ("particle_x", "particle_v", "particle_C", "particle_mass")
-        n = n_p if whole else (n_e if f == "particle_d" else n_nv)
-        g = np.zeros((n,) + parts[0][f].shape[1:], np.float32)
-        filled = np.zeros(n, bool)
+        g = np.zeros((size[cls],) + parts[0][f].shape[1:], np.float32)
+        filled = np.zeros(size[cls], bool)
         for p in parts:
-            ids = p["all_ids"] if whole else (p["e_ids"] if f == "particle_d" else p["nv_ids"])
+            ids = p[cls + "_ids"]
             g[ids] = p[f]
             filled[ids] = True
         assert filled.all(), f"{f}: {int((~filled).sum())} particles have no owner"
@@ -399,70 +515,51 @@ def assemble_global(parts, sc: Scene) -> dict:
 
 def gather_global_state(ss: "ShardedSim") -> dict:
     """Collective: the current state of every particle, assembled from its owner, in the global (unsharded) order."""
-    import torch.distributed as dist
-    st, md, sh, sc = ss.sim.state, ss.sim.model, ss.shard, ss.global_scene
-    local = {f: getattr(st, f).detach().cpu().numpy() for f in _CARRY_FIELDS}
-    local.update({f: getattr(md, f).detach().cpu().numpy() for f in _CARRY_MODEL})
-    parts = [None] * sh.world
-    dist.all_gather_object(parts, owned_slices(local, sh, sc))
-    return assemble_global(parts, sc)
+    holder = {"state": ss.sim.state, "model": ss.sim.model}
+    local = {f: getattr(holder[where], f).detach().cpu().numpy() for f, (where, _) in CARRIED.items()}
+    parts = [None] * ss.shard.world
+    dist.all_gather_object(parts, owned_slices(local, ss.shard, ss.global_scene))
+    return assemble_global(parts, ss.global_scene)
 
 
 def _apply_carry(sim, shard: Shard, sc: Scene, carry: dict):
     """Write the carried state of this rank's (owned and ghost) particles into the freshly built local solver."""
-    import torch
-    st, md = sim.state, sim.model
-    ne_g, nt_g = sc.n_elements, sc.n_traditional
-    el = np.concatenate([shard.own_e, shard.ghost_e])
-    vl = np.concatenate([shard.own_v, shard.ghost_v])
-    t_ids = np.where(shard.t_gid >= 0, shard.t_gid, shard.own_t[0] if shard.own_t.size else 0)   # (free rows: any valid particle's state)
-    all_ids = np.concatenate([el, ne_g + t_ids, ne_g + nt_g + vl])
-    nv_ids = np.concatenate([el, ne_g + t_ids])
-    dev = st.particle_x.device
-    put = lambda dst, a: dst.copy_(torch.as_tensor(np.ascontiguousarray(a, np.float32), device=dev).reshape(dst.shape)) if dst.numel() else None
-    for f in ("particle_C", "particle_mass"):
-        put(getattr(st, f), carry[f][all_ids])
-    for f in ("particle_F", "particle_F_trial", "particle_stress"):
-        put(getattr(st, f), carry[f][nv_ids])
-    for f in _CARRY_MODEL:
-        put(getattr(md, f), carry[f][all_ids])
+    holder = {"state": sim.state, "model": sim.model}
+    ids = dict(zip(("all", "nv"), shard.local_ids(sc)))
+    dev = sim.state.particle_x.device
+    for f, (where, cls) in CARRIED.items():
+        if f in _CARRIED_BY_THE_SCENE:
+            continue
+        dst = getattr(holder[where], f)
+        if dst.numel():
+            dst.copy_(torch.as_tensor(np.ascontiguousarray(carry[f][ids[cls]], np.float32), device=dev).reshape(dst.shape))
     sim.solver.time = carry["time"]
 
 
 def slab_leavers(ss: "ShardedSim") -> float:
     """Collective: fraction of all vertices / traditional particles that sit outside the x-slab of the rank that owns them.
     Counted on the device (no copy of the positions to the host); one two-element all-reduce."""
-    import torch
-    import torch.distributed as dist
     sh = ss.shard
-    xs = _owned_movable_x(ss)
+    xs = owned_movable_x(sh, ss.sim.state.particle_x.detach())
     n_own = sh.own_t.size + sh.own_v.size
     lo = -np.inf if sh.rank == 0 else float(sh.cuts[sh.rank - 1])
     hi = np.inf if sh.rank == sh.world - 1 else float(sh.cuts[sh.rank])
     out = ((xs < lo) | (xs >= hi)).sum().to(torch.float64)
-    # (collectives run at world size 1 too: a tensor on the wrong device for the backend -- NCCL takes no CPU tensors --
-    # then fails on a one-GPU test box and not first on the node)
     t = torch.stack([out, torch.tensor(float(n_own), dtype=torch.float64, device=out.device)])
-    t = t.cpu() if ss.backend == "gloo" else t
-    dist.all_reduce(t)
-    t = t.cpu()
-    return float(t[0] / max(float(t[1]), 1.0))
+    n_out, n_all = _all_reduce(ss.backend, ss.device, t).tolist()
+    return n_out / max(n_all, 1.0)
 
 
 def halo_bytes_max(ss: "ShardedSim") -> int:
     """Collective: max over the ranks of the bytes a rank sends per substep in the halo exchange (shared blocks x channels x 256 B),
     as of the last collective re-sort."""
-    import torch
-    import torch.distributed as dist
     if ss.transport == "rccl":
         hb = C.c_int64(0)
         ss.sim.solver._call("mpmhip_dist_halo_bytes", C.byref(hb))
         mine = int(hb.value)
     else:
-        mine = 4 * sum(int(p["n_halo"]) for p in ss.peers)
-    t = torch.tensor([mine], dtype=torch.int64, device="cpu" if ss.backend == "gloo" else ss.sim.solver.device)
-    dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    return int(t.item())
+        mine = 4 * sum(p.n_halo for p in ss.peers)
+    return _all_reduce(ss.backend, ss.device, [mine], op=dist.ReduceOp.MAX, dtype=torch.int64)[0]
 
 
 # --------------------------------------------------------------------------------------------- on-device migration (traditional particles)
@@ -475,14 +572,29 @@ MIG_RECORD_FLOATS = sum(w for _, w in _MIG_STATE) + len(_MIG_MODEL)   # 52 float
 def _mig_tensors(ss: "ShardedSim"):
     """The per-particle float tensors a traditional particle's record is made of, each as a [local traditional rows, width] VIEW of the
     caller-order tensor the solver is bound to."""
-    st, md, sh = ss.sim.state, ss.sim.model, ss.shard
-    ne_l, nt_l = sh.own_e.size + sh.ghost_e.size, sh.t_gid.size
-    out = []
-    for name, w in _MIG_STATE:
-        out.append(st._raw(name).detach().reshape(-1, w)[ne_l:ne_l + nt_l])
-    for name in _MIG_MODEL:
-        out.append(md._raw(name).detach().reshape(-1, 1)[ne_l:ne_l + nt_l])
-    return out
+    st, md, rows = ss.sim.state, ss.sim.model, ss.shard.trad_rows
+    return ([st._raw(name).detach().reshape(-1, w)[rows] for name, w in _MIG_STATE]
+            + [md._raw(name).detach().reshape(-1, 1)[rows] for name in _MIG_MODEL])
+
+
+def _exchange_records_through_the_host(rank: int, world: int, dev, outgoing, out_split, in_split):
+    """The all-to-all of migrate_traditional for gloo, which has none: every tensor of `outgoing` ([n_out, ...], rows grouped by
+    destination) goes point-to-point, batched, staged through host memory like every other exchange of the test backend."""
+    src = [list(t.cpu().split(out_split)) for t in outgoing]
+    dst = [[torch.empty((c,) + t.shape[1:], dtype=t.dtype) for c in in_split] for t in outgoing]
+    ops = []
+    for q in range(world):
+        if q == rank:
+            continue
+        for s, d in zip(src, dst):
+            if s[q].numel():
+                ops.append(dist.P2POp(dist.isend, s[q].contiguous(), q))
+            if d[q].numel():
+                ops.append(dist.P2POp(dist.irecv, d[q], q))
+    if ops:
+        for req in dist.batch_isend_irecv(ops):
+            req.wait()
+    return [torch.cat(d).to(dev) for d in dst]
 
 
 def migrate_traditional(ss: "ShardedSim", min_fraction: float = 0.0) -> int:
@@ -496,8 +608,6 @@ def migrate_traditional(ss: "ShardedSim", min_fraction: float = 0.0) -> int:
     see maybe_repartition).
     Returns the number of particles that changed rank (all ranks: the same number); 0 when fewer than min_fraction of the traditional
     particles would move; -1 when some rank has too few free rows (nothing is changed then: the caller falls back to repartition())."""
-    import torch
-    import torch.distributed as dist
     sh, sim = ss.shard, ss.sim
     sc = ss.global_scene
     world, rank = sh.world, sh.rank
@@ -505,9 +615,6 @@ def migrate_traditional(ss: "ShardedSim", min_fraction: float = 0.0) -> int:
         return 0
     sv, st = sim.solver, sim.state
     dev = st._raw("particle_x").device
-    host = ss.backend == "gloo"
-    import os
-    import time
     marks = []
 
     def mark(what):   # MPMHIP_VERBOSE=2: where a migration event's time goes (synchronises the device at every mark)
@@ -522,50 +629,33 @@ def migrate_traditional(ss: "ShardedSim", min_fraction: float = 0.0) -> int:
     cuts = torch.as_tensor(cuts_np, dtype=torch.float32, device=dev)
     gid = torch.as_tensor(sh.t_gid, dtype=torch.int64, device=dev)
     owned = gid >= 0
-    fields = _mig_tensors(ss)
-    x = fields[0][:, 0]
+    cols = _mig_tensors(ss)
+    x = cols[0][:, 0]
     dest = torch.bucketize(x.contiguous(), cuts, right=True)       # = np.searchsorted(cuts, x, side="right"), the rule of _owners()
     move = owned & (dest != rank)
     out_counts = torch.bincount(dest[move], minlength=world).to(torch.int64)
-    table = [torch.zeros(world, dtype=torch.int64, device="cpu" if host else dev) for _ in range(world)]
-    dist.all_gather(table, out_counts.cpu() if host else out_counts)
-    table = torch.stack(table).cpu().numpy()            # table[src][dst]
+    table = torch.stack(_all_gather(ss.backend, out_counts, world)).cpu().numpy()            # table[src][dst]
     n_moving = int(table.sum())
     n_in = int(table[:, rank].sum())
     n_free = int((~owned).sum().item())
-    ok = torch.tensor([1 if n_in <= n_free + int(table[rank].sum()) else 0], dtype=torch.int32, device="cpu" if host else dev)
-    dist.all_reduce(ok, op=dist.ReduceOp.MIN)
+    room = _all_reduce(ss.backend, dev, [1 if n_in <= n_free + int(table[rank].sum()) else 0], op=dist.ReduceOp.MIN) == [1]
     mark("counts")
     if n_moving == 0 or n_moving < min_fraction * sc.n_traditional:
         return 0
-    if int(ok.item()) != 1:
+    if not room:
         return -1
     # records of the leavers, grouped by destination (stable: ascending row inside a group)
     idx = torch.nonzero(move).reshape(-1)
     idx = idx[torch.sort(dest[idx], stable=True).indices]
-    rec = torch.cat([f[idx] for f in fields], dim=1).contiguous()
+    rec = torch.cat([f[idx] for f in cols], dim=1).contiguous()
     rec_id = gid[idx].contiguous()
     out_split = [int(c) for c in table[rank]]
     in_split = [int(c) for c in table[:, rank]]
-    rec_in = torch.empty((n_in, MIG_RECORD_FLOATS), dtype=torch.float32, device=dev)
-    id_in = torch.empty(n_in, dtype=torch.int64, device=dev)
-    if host:   # gloo: staged through host memory like every other exchange of the test backend
-        ro, io = list(rec.cpu().split(out_split)), list(rec_id.cpu().split(out_split))
-        ri, ii = [torch.empty((c, MIG_RECORD_FLOATS)) for c in in_split], [torch.empty(c, dtype=torch.int64) for c in in_split]
-        ops = []   # (gloo has no all-to-all: point-to-point, batched)
-        for q in range(world):
-            if q == rank:
-                continue
-            for src, dst in ((ro, ri), (io, ii)):
-                if src[q].numel():
-                    ops.append(dist.P2POp(dist.isend, src[q].contiguous(), q))
-                if dst[q].numel():
-                    ops.append(dist.P2POp(dist.irecv, dst[q], q))
-        if ops:
-            for req in dist.batch_isend_irecv(ops):
-                req.wait()
-        rec_in, id_in = torch.cat(ri).to(dev), torch.cat(ii).to(dev)
+    if ss.backend == "gloo":
+        rec_in, id_in = _exchange_records_through_the_host(rank, world, dev, (rec, rec_id), out_split, in_split)
     else:
+        rec_in = torch.empty((n_in, MIG_RECORD_FLOATS), dtype=torch.float32, device=dev)
+        id_in = torch.empty(n_in, dtype=torch.int64, device=dev)
         dist.all_to_all_single(rec_in, rec, in_split, out_split)
         dist.all_to_all_single(id_in, rec_id, in_split, out_split)
     mark("exchange")
@@ -573,7 +663,7 @@ def migrate_traditional(ss: "ShardedSim", min_fraction: float = 0.0) -> int:
     gid[idx] = -1
     free_rows = torch.nonzero(gid < 0).reshape(-1)[:n_in]
     off = 0
-    for f in fields:
+    for f in cols:
         w = f.shape[1]
         f[free_rows] = rec_in[:, off:off + w]
         off += w
@@ -581,12 +671,11 @@ def migrate_traditional(ss: "ShardedSim", min_fraction: float = 0.0) -> int:
     mark("insert")
     # sorted layout: free rows first, owned rows by ascending global id
     order = torch.sort(gid, stable=True).indices
-    for f in fields:
+    for f in cols:
         f.copy_(f[order])
     gid = gid[order]
-    ne_l = sh.own_e.size + sh.ghost_e.size
     sel = st._raw("particle_selection")
-    sel[ne_l:ne_l + gid.numel()] = (gid < 0).to(sel.dtype)      # 1: free row (never simulated), 0: owned
+    sel[sh.trad_rows] = (gid < 0).to(sel.dtype)         # 1: free row (never simulated), 0: owned
     mark("sort rows")
     sh.t_gid = gid.cpu().numpy()
     sh.own_t = sh.t_gid[sh.t_gid >= 0]
@@ -609,52 +698,40 @@ def repartition(ss: "ShardedSim") -> "ShardedSim":
     (state, solver time and substep count carried over).  The ShardedSim is updated IN PLACE (and returned): a caller that
     keeps its reference without rebinding continues on the new shard.  The old solver context -- with its RCCL communicator
     and peer-mapped arenas -- is destroyed before the new shard is built, so the two never coexist."""
-    import sys
-    import torch
-    import torch.distributed as dist
     sc = ss.global_scene
     cuts = device_cuts(ss)                      # (before the state leaves the device: histogram of the owned particles' x)
     carry = gather_global_state(ss)
     carry["time"] = ss.sim.solver.time
     new_sc = replace(sc, x=carry["particle_x"], v=carry["particle_v"], d=carry["particle_d"])
-    dev = str(ss.sim.solver.device)
-    keep = dict(steps_done=ss.steps_done, resorts=ss.resorts, migrate_fraction=ss.migrate_fraction, migrations=ss.migrations + 1,
-                migrate_halo_factor=ss.migrate_halo_factor, halo_ref=0, migrate_trad_fraction=ss.migrate_trad_fraction,
-                trad_migrations=ss.trad_migrations, trad_migrated=ss.trad_migrated, trad_migration_ms=ss.trad_migration_ms,
-                migrate_check_every=ss.migrate_check_every, migrate_checked_at=ss.migrate_checked_at)
-    rank, world, rebin_interval = ss.shard.rank, ss.shard.world, ss.rebin_interval
+    rank, world = ss.shard.rank, ss.shard.world
     old = ss.sim
-    ss.sim, ss.peers, ss.keep, ss.static = None, [], [], {}     # drop every tensor the old context was handed ...
-    for name in ("keep_body", "keep_jt", "keep_body_frame"):
-        ss.__dict__.pop(name, None)
+    # drop every tensor the old context was handed ...
+    ss.sim, ss.peers, ss.static, ss.body_pose, ss.held_buf = None, [], None, None, None
     old.solver.close()                                          # ... and the context itself (communicator, IPC arenas)
     del old
     # The rebuild can fail on ONE rank (out of memory, a peer link that does not come up): that rank must not be left with
     # sim = None while the others wait in the next collective (ADVICE r3).  Every rank reports, the minimum decides, all raise.
     new, err = None, None
     try:
-        new = build_sharded(new_sc, dev, rank, world, rebin_interval=rebin_interval, _carry=carry, _cuts=cuts)
+        new = build_sharded(new_sc, str(ss.device), rank, world, rebin_interval=ss.rebin_interval, _carry=carry, _cuts=cuts)
     except Exception as e:  # noqa: BLE001 - reported collectively below
         err = e
-    ok = torch.tensor([0 if new is None else 1], dtype=torch.int32, device="cpu" if ss.backend == "gloo" else dev)
-    dist.all_reduce(ok, op=dist.ReduceOp.MIN)
-    if int(ok.item()) != 1:
+    if _all_reduce(ss.backend, ss.device, [0 if new is None else 1], op=dist.ReduceOp.MIN) != [1]:
         if new is not None:
             new.sim.solver.close()
-        msg = f"re-partition at substep {keep['steps_done']} failed on " + ("this rank: " + repr(err) if err is not None else "another rank")
+        msg = f"re-partition at substep {ss.steps_done} failed on " + ("this rank: " + repr(err) if err is not None else "another rank")
         print(f"[mpmavatar_amd.dist] rank {rank}: {msg}", file=sys.stderr, flush=True)
         raise RuntimeError("mpmavatar_amd.dist.repartition: " + msg + " (every rank raises; the sharded simulation is gone -- "
                            "rebuild it from a checkpoint of gather_global_state)") from err
-    ss.__dict__.update(new.__dict__)
-    for k, v in keep.items():
-        setattr(ss, k, v)
-    ss.sim.steps_done = keep["steps_done"]
+    for f in fields(PartitionState):            # the fresh partition; RunState stays as it is, but for:
+        setattr(ss, f.name, getattr(new, f.name))
+    ss.halo_ref = 0
+    ss.migrations += 1
+    ss.sim.steps_done = ss.steps_done
     return ss
 
 
 def maybe_repartition(ss: "ShardedSim") -> "ShardedSim":
-    import os
-    import sys
     if (ss.migrate_fraction <= 0 and ss.migrate_trad_fraction < 0) or ss.shard.world == 1 or ss.steps_done == 0:
         return ss
     if ss.steps_done - ss.migrate_checked_at < ss.migrate_check_every:
@@ -670,8 +747,6 @@ def maybe_repartition(ss: "ShardedSim") -> "ShardedSim":
     # (0) traditional particles that have mixed across the cuts change rank ON THE DEVICE (migrate_traditional): cheap enough to do at
     # every look, and what it does not fix (too few free rows; cloth folded across a cut) is left to the halo criterion below
     if ss.migrate_trad_fraction >= 0 and ss.global_scene.n_traditional > 0:
-        import time
-        import torch
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         moved = migrate_traditional(ss, ss.migrate_trad_fraction)
@@ -707,8 +782,6 @@ def maybe_repartition(ss: "ShardedSim") -> "ShardedSim":
 def _init_rccl(ss: ShardedSim, rank: int, world: int):
     """Create the library's own RCCL communicator (unique id from rank 0, broadcast through torch.distributed) and hand
     it the static ghost lists."""
-    import torch.distributed as dist
-    from . import _lib as L
     sv, sh = ss.sim.solver, ss.shard
     uid = (C.c_char * 128)()
     if rank == 0:
@@ -736,78 +809,65 @@ def _init_rccl(ss: ShardedSim, rank: int, world: int):
 
 
 def _all_gather_maps(ss: ShardedSim):
-    import torch
-    import torch.distributed as dist
-    m = ss.static["map"]
-    world = ss.shard.world
-    if ss.backend == "gloo":
-        mc = m.cpu()
-        outs = [torch.zeros_like(mc) for _ in range(world)]
-        dist.all_gather(outs, mc)
-        return [o.to(m.device) for o in outs]
-    outs = [torch.zeros_like(m) for _ in range(world)]
-    dist.all_gather(outs, m)
-    return outs
+    """Collective: every rank's active-block map, on this rank's device."""
+    m = ss.static.block_map
+    return [o.to(m.device) for o in _all_gather(ss.backend, m, ss.shard.world)]
 
 
 def rebin_all(ss: ShardedSim):
     """Collective: every rank re-sorts and rebuilds the shared-block lists with each peer."""
-    import torch
-    from . import _lib as L
     sv = ss.sim.solver
-    sv._call("mpmhip_dist_rebin", ss.static["map"].data_ptr())
+    sv._call("mpmhip_dist_rebin", ss.static.block_map.data_ptr())
     maps = _all_gather_maps(ss)
     mine = maps[ss.shard.rank]
-    ch = 8 if sv.particle_movers else 4
-    peers, keep = [], []
-    arr = []
+    ch = halo_channels(sv.particle_movers)
+    peers, arr = [], []
     for q in range(ss.shard.world):
         if q == ss.shard.rank:
             continue
         blocks = torch.nonzero(mine & maps[q]).reshape(-1).to(torch.int32)
-        st = ss.static.get(q)
-        if blocks.numel() == 0 and st is None:
+        g = ss.static.ghosts.get(q)
+        if blocks.numel() == 0 and g is None:
             continue
         nb = int(blocks.numel())
-        hs = torch.zeros(max(nb * ch * 64, 1), dtype=torch.float32, device=mine.device)
+        hs = torch.zeros(max(halo_floats(nb, ch), 1), dtype=torch.float32, device=mine.device)
         hr = torch.zeros_like(hs)
-        keep += [blocks, hs, hr]
         p = L.DistPeer()
         p.n_blocks, p.blocks, p.halo_send, p.halo_recv = nb, blocks.data_ptr() if nb else None, hs.data_ptr(), hr.data_ptr()
-        if st is not None:
-            p.n_send_p, p.n_recv_p = st["send_p"].numel(), st["recv_p"].numel()
-            p.n_send_e, p.n_recv_e = st["send_e"].numel(), st["recv_e"].numel()
-            p.send_p, p.recv_p = st["send_p"].data_ptr(), st["recv_p"].data_ptr()
-            p.send_e, p.recv_e = st["send_e"].data_ptr(), st["recv_e"].data_ptr()
-            p.ghost_send, p.ghost_recv = st["gs"].data_ptr(), st["gr"].data_ptr()
+        if g is not None:
+            p.n_send_p, p.n_recv_p = g.send_p.numel(), g.recv_p.numel()
+            p.n_send_e, p.n_recv_e = g.send_e.numel(), g.recv_e.numel()
+            p.send_p, p.recv_p = g.send_p.data_ptr(), g.recv_p.data_ptr()
+            p.send_e, p.recv_e = g.send_e.data_ptr(), g.recv_e.data_ptr()
+            p.ghost_send, p.ghost_recv = g.gs.data_ptr(), g.gr.data_ptr()
         arr.append(p)
-        peers.append(dict(rank=q, hs=hs, hr=hr, n_halo=nb * ch * 64,
-                          gs=None if st is None else st["gs"], gr=None if st is None else st["gr"],
-                          n_gs=0 if st is None else 6 * st["send_p"].numel() + 3 * st["send_e"].numel(),
-                          n_gr=0 if st is None else 6 * st["recv_p"].numel() + 3 * st["recv_e"].numel()))
+        peers.append(Peer(q, blocks, hs, hr, halo_floats(nb, ch), g))
     carr = (L.DistPeer * max(len(arr), 1))(*arr)
     sv._call("mpmhip_dist_set_peers", len(arr), carr)
-    ss.peers, ss.keep = peers, keep
+    ss.peers = peers
 
 
 def _exchange(ss: ShardedSim, kind: str):
-    import torch
-    import torch.distributed as dist
     ops, post = [], []
     for p in ss.peers:
-        sbuf, rbuf, ns, nr = (p["hs"], p["hr"], p["n_halo"], p["n_halo"]) if kind == "halo" else (p["gs"], p["gr"], p["n_gs"], p["n_gr"])
+        if kind == "halo":
+            sbuf, rbuf, ns, nr = p.hs, p.hr, p.n_halo, p.n_halo
+        elif p.ghosts is not None:
+            sbuf, rbuf, ns, nr = p.ghosts.gs, p.ghosts.gr, p.ghosts.n_send, p.ghosts.n_recv
+        else:
+            continue
         if ss.backend == "gloo":
             if ns:
-                ops.append(dist.P2POp(dist.isend, sbuf[:ns].cpu(), p["rank"]))
+                ops.append(dist.P2POp(dist.isend, sbuf[:ns].cpu(), p.rank))
             if nr:
                 tmp = torch.empty(nr, dtype=torch.float32)
-                ops.append(dist.P2POp(dist.irecv, tmp, p["rank"]))
+                ops.append(dist.P2POp(dist.irecv, tmp, p.rank))
                 post.append((rbuf, tmp, nr))
         else:
             if ns:
-                ops.append(dist.P2POp(dist.isend, sbuf[:ns], p["rank"]))
+                ops.append(dist.P2POp(dist.isend, sbuf[:ns], p.rank))
             if nr:
-                ops.append(dist.P2POp(dist.irecv, rbuf[:nr], p["rank"]))
+                ops.append(dist.P2POp(dist.irecv, rbuf[:nr], p.rank))
     if ops:
         for req in dist.batch_isend_irecv(ops):
             req.wait()
@@ -817,14 +877,9 @@ def _exchange(ss: ShardedSim, kind: str):
 
 def _any_rank_drifting(ss: ShardedSim) -> bool:
     """Collective: max over the ranks of the library's early-warning drift flag."""
-    import torch
-    import torch.distributed as dist
-    sv = ss.sim.solver
     flag = C.c_int32(0)
-    sv._call("mpmhip_dist_drift_flag", C.byref(flag))
-    t = torch.tensor([flag.value], dtype=torch.int32, device="cpu" if ss.backend == "gloo" else sv.device)
-    dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    return bool(int(t.item()))
+    ss.sim.solver._call("mpmhip_dist_drift_flag", C.byref(flag))
+    return _all_reduce(ss.backend, ss.device, [flag.value], op=dist.ReduceOp.MAX) != [0]
 
 
 def _held_local(ss: ShardedSim, step: int) -> int:
@@ -836,77 +891,71 @@ def _held_local(ss: ShardedSim, step: int) -> int:
     return int((sh.own_t >= sc.n_traditional - sc.joint_t_count(step)).sum())
 
 
+def _body_at(ss: ShardedSim, step: int):
+    """(mesh_x at substep 0 of the library's advection x + (step dt) v, mesh_v, joint_verts_v, joint_faces_v) valid at
+    `step`.  A body posed per frame (Scene.mesh_sway, train_material_params.py:617-622) has a new velocity every frame:
+    the frame's start pose is extrapolated back to substep 0 with that velocity, so that the same absolute advection
+    factor (step_index + k) dt reproduces pose(frame start) + (step - frame start) dt v."""
+    sim, gsc = ss.sim, ss.global_scene
+    jv, jf = sim.joint_verts_v, sim.joint_faces_v
+    if gsc.mesh_sway is None or sim.mesh_x0 is None:
+        return sim.mesh_x0, sim.mesh_v, jv, jf
+    f0, _ = gsc.frame_of(step)
+    if ss.body_pose is None or ss.body_pose.frame != f0:
+        dev = sim.solver.device
+        t3 = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float32), device=dev).reshape(-1, 3)
+        mx, mv = gsc.body_at(f0)
+        x0 = (mx.astype(np.float64) - gsc.dt * f0 * mv.astype(np.float64)).astype(np.float32)
+        if jv is not None:
+            vel = torch.as_tensor(np.ascontiguousarray(mv[0], np.float32), device=dev)
+            jv, jf = vel.expand(jv.shape[0], 3).contiguous(), vel.expand(jf.reshape(-1, 3).shape[0], 3).contiguous()
+        ss.body_pose = BodyPose(f0, (t3(x0), t3(mv), jv, jf))
+    return ss.body_pose.tensors
+
+
+def _step_pointers(ss: ShardedSim, step: int):
+    """The arguments of a substep call that depend on the substep: device addresses of the body's (mesh_x, mesh_v), of the held
+    particles' velocities with their count, of the joints' velocities (an empty joint list still gets an address)."""
+    dp = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+    joint = lambda t: None if t is None else (dp(t) or ss.sim.solver._dummy_ptr())
+    bx, bv, bjv, bjf = _body_at(ss, step)
+    h = _held_local(ss, step)
+    return dp(bx), dp(bv), ss.held_buf.data_ptr() if h > 0 else None, max(h, 0), joint(bjv), joint(bjf)
+
+
 def run(ss: ShardedSim, n_steps: int):
     # NOTE: the migration check (maybe_repartition) runs at the START of a call only, every `migrate_check_every` (512) substeps of
     # accumulated progress: run(ss, n) with a large n never re-partitions mid-call -- callers that expect particles to cross slabs
     # advance in frames (the reference's drivers call per frame of 400 substeps anyway).
     """Advance n substeps on every rank (collective).  Returns ``ss`` (a re-partition updates it in place)."""
-    import torch
     ss = maybe_repartition(ss)
-    sim, sv, sc = ss.sim, ss.sim.solver, ss.sim.scene
-    mt = sim.state._raw("particle_mass")
+    sv, sc = ss.sim.solver, ss.sim.scene
+    mt = ss.sim.state._raw("particle_mass")
     if (mt.data_ptr(), mt._version) != ss.mass_version:   # masses rewritten since the ranks last agreed (reset_density(update_mass))
         sync_mass_span(ss)                                    # (collective: every rank rewrites its masses through the same caller code)
-    dp = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
-    jv, jf = sim.joint_verts_v, sim.joint_faces_v
-    dummy = sv._dummy_ptr()
     if sv._host_dt != sc.dt:  # MPMWARP.time advances by the Python float (mpm_solver.py:536)
         sv._call("mpmhip_set_host_dt", float(sc.dt))
         sv._host_dt = sc.dt
-    held = lambda step: _held_local(ss, step)
-    gsc = ss.global_scene
-    swaying = getattr(gsc, "mesh_sway", None) is not None and sim.mesh_x0 is not None
-    t3 = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float32), device=sv.device).reshape(-1, 3)
-
-    def body(step):
-        """(mesh_x at substep 0 of the library's advection x + (step dt) v, mesh_v, joint_verts_v, joint_faces_v) valid at
-        `step`.  A body posed per frame (Scene.mesh_sway, train_material_params.py:617-622) has a new velocity every frame:
-        the frame's start pose is extrapolated back to substep 0 with that velocity, so that the same absolute advection
-        factor (step_index + k) dt reproduces pose(frame start) + (step - frame start) dt v."""
-        if not swaying:
-            return sim.mesh_x0, sim.mesh_v, jv, jf
-        f0, _ = gsc.frame_of(step)
-        if getattr(ss, "keep_body_frame", None) == f0:
-            return ss.keep_body
-        ss.keep_body_frame = f0
-        mx, mv = gsc.body_at(f0)
-        x0 = (mx.astype(np.float64) - gsc.dt * f0 * mv.astype(np.float64)).astype(np.float32)
-        bjv, bjf = jv, jf
-        if jv is not None:
-            vel = torch.as_tensor(np.ascontiguousarray(mv[0], np.float32), device=sv.device)
-            bjv, bjf = vel.expand(jv.shape[0], 3).contiguous(), vel.expand(jf.reshape(-1, 3).shape[0], 3).contiguous()
-        ss.keep_body = (t3(x0), t3(mv), bjv, bjf)   # alive until the next frame's tensors replace them
-        return ss.keep_body
-
-    def frame_run(step, n):
-        """Substeps from `step` that share one body pose / velocity."""
-        if not swaying:
-            return n
-        f0, spf = gsc.frame_of(step)
-        return min(n, f0 + spf - step)
-    jt_buf = None
     if ss.global_scene.joint_t_hold > 0:
-        jt_buf = torch.zeros((max(ss.shard.t_gid.size, 1), 3), dtype=torch.float32, device=sv.device)
-        ss.keep_jt = jt_buf
-    if ss.transport == "rccl":
-        jvp = None if jv is None else (dp(jv) or dummy)
-        jfp = None if jf is None else (dp(jf) or dummy)
-        k = 0
-        while k < n_steps:  # runs of substeps over which the number of held particles does not change
-            n = n_steps - k
-            h = held(ss.steps_done)
-            if h >= 0:
-                n = next((j for j in range(1, n) if held(ss.steps_done + j) != h), n)
-            n = frame_run(ss.steps_done, n)
-            bx, bv, bjv, bjf = body(ss.steps_done)
-            if swaying:
-                jvp = None if bjv is None else (dp(bjv) or dummy)
-                jfp = None if bjf is None else (dp(bjf) or dummy)
-            sv._call("mpmhip_rccl_steps", float(sc.dt), int(n), int(ss.steps_done), int(ss.rebin_interval),
-                     dp(bx), dp(bv), jt_buf.data_ptr() if h > 0 else None, max(h, 0), jvp, jfp)
-            ss.steps_done += n
-            k += n
-        return ss
+        ss.held_buf = torch.zeros((max(ss.shard.t_gid.size, 1), 3), dtype=torch.float32, device=sv.device)
+    (_run_in_library if ss.transport == "rccl" else _run_python_driven)(ss, n_steps)
+    return ss
+
+
+def _run_in_library(ss: ShardedSim, n_steps: int):
+    """mpmhip_rccl_steps, once per run of substeps that share one held count and one body pose (Scene.fused_run)."""
+    sv, sc = ss.sim.solver, ss.sim.scene
+    end = ss.steps_done + n_steps
+    while ss.steps_done < end:
+        n = ss.global_scene.fused_run(ss.steps_done, end - ss.steps_done, count=lambda step: _held_local(ss, step))
+        bx, bv, jt, n_jt, jvp, jfp = _step_pointers(ss, ss.steps_done)
+        sv._call("mpmhip_rccl_steps", float(sc.dt), int(n), int(ss.steps_done), int(ss.rebin_interval), bx, bv, jt, n_jt, jvp, jfp)
+        ss.steps_done += n
+
+
+def _run_python_driven(ss: ShardedSim, n_steps: int):
+    """The three phases of every substep called from here, the exchanges between them through torch.distributed."""
+    sv, sc = ss.sim.solver, ss.sim.scene
     adaptive = ss.rebin_interval <= 0   # re-sort when any rank's drift flag asks for it (polled every 16 substeps)
     cap = -ss.rebin_interval if ss.rebin_interval < 0 else (256 if ss.rebin_interval == 0 else ss.rebin_interval)
     for _ in range(n_steps):
@@ -921,12 +970,8 @@ def run(ss: ShardedSim, n_steps: int):
             ss.since, ss.resort_now, ss.sorted_once = 0, False, True
             ss.resorts += 1
         adv = float(np.float32(sc.dt * ss.steps_done))
-        bx, bv, bjv, bjf = body(ss.steps_done)
-        jvp = None if bjv is None else (dp(bjv) or dummy)
-        jfp = None if bjf is None else (dp(bjf) or dummy)
-        h = held(ss.steps_done)
-        sv._call("mpmhip_dist_step_begin", float(sc.dt), dp(bx), dp(bv), adv,
-                 jt_buf.data_ptr() if h > 0 else None, max(h, 0), jvp, jfp)
+        bx, bv, jt, n_jt, jvp, jfp = _step_pointers(ss, ss.steps_done)
+        sv._call("mpmhip_dist_step_begin", float(sc.dt), bx, bv, adv, jt, n_jt, jvp, jfp)
         _exchange(ss, "halo")
         sv._call("mpmhip_dist_step_mid")
         if not ss.ghost_g2p:
@@ -936,14 +981,12 @@ def run(ss: ShardedSim, n_steps: int):
         ss.since += 1
         if adaptive and ss.since % 16 == 0:
             ss.resort_now = _any_rank_drifting(ss)
-    return ss
 
 
 def gather_positions(ss: ShardedSim):
     """Owned particle positions with their global ids (for tests): (elements, traditional, vertices)."""
-    st, sh, sc = ss.sim.state, ss.shard, ss.sim.scene
-    x = st.particle_x.detach().cpu().numpy()
-    ne, nt = sc.n_elements, sc.n_traditional
-    t_loc = np.nonzero(sh.t_gid >= 0)[0]
-    return dict(e_id=sh.own_e, e_x=x[:sh.own_e.size], t_id=sh.t_gid[t_loc], t_x=x[ne + t_loc],
-                v_id=sh.own_v, v_x=x[ne + nt:ne + nt + sh.own_v.size])
+    sh = ss.shard
+    x = ss.sim.state.particle_x.detach().cpu().numpy()
+    t_loc = sh.own_trad
+    return dict(e_id=sh.own_e, e_x=x[:sh.own_e.size], t_id=sh.t_gid[t_loc], t_x=x[sh.trad_rows][t_loc],
+                v_id=sh.own_v, v_x=x[sh.own_vertex_rows])

@@ -74,8 +74,8 @@ def build_solver(sc: Scene, device="cuda:0", mode=None, rebin_interval=0, p2g_ti
 
 def run(sim: Sim, n_steps: int, fused: bool = False):
     """Advance ``n_steps`` substeps.  fused=False issues one ``p2g2p`` per substep with the mesh advected
-    on the torch side like the reference loop; fused=True hands runs of substeps to ``mpmhip_steps`` (split where the
-    scene's staged sand release changes the length of ``joint_traditional_v``)."""
+    on the torch side like the reference loop; fused=True hands runs of substeps to ``mpmhip_steps`` (split as
+    ``Scene.fused_run`` says)."""
     sc, sv = sim.scene, sim.solver
     dev = sv.device  # (not via sim.state.particle_x: reading a state field pulls it back and forces a re-import)
 
@@ -104,13 +104,7 @@ def run(sim: Sim, n_steps: int, fused: bool = False):
         k0 = sim.steps_done
         n = 1
         if fused:
-            n = end - k0
-            if sc.joint_t_hold > 0:  # stop the fused run at the next change of the held count
-                c0 = sc.joint_t_count(k0)
-                n = next((j for j in range(1, n) if sc.joint_t_count(k0 + j) != c0), n)
-            f0, spf = sc.frame_of(k0)
-            if spf is not None:      # ... and at the next pose of a swaying body (the fused call advects x + k dt v)
-                n = min(n, f0 + spf - k0)
+            n = sc.fused_run(k0, end - k0)
             mx, mv = mesh(k0)
             sv.p2g2p_n(sim.model, sim.state, sc.dt, n, mesh_x=mx, mesh_v=mv, **kwargs(k0))
         else:

@@ -78,6 +78,20 @@ class Scene:
         spf = int(self.mesh_sway[2])
         return (step // spf) * spf, spf
 
+    def fused_run(self, step: int, n: int, count=None) -> int:
+        """How many of the n substeps from `step` one fused call may cover: it stops where the held count of the staged sand
+        release changes (the call takes ONE joint_traditional_v) and at the next pose of a body posed per frame (the call advects
+        x + k dt v with one velocity).  count: the held count as a function of the substep -- this scene's joint_t_count, or a
+        sharded rank's share of it."""
+        if self.joint_t_hold > 0:
+            count = count or self.joint_t_count
+            c0 = count(step)
+            n = next((j for j in range(1, n) if count(step + j) != c0), n)
+        f0, spf = self.frame_of(step)
+        if spf is not None:
+            n = min(n, f0 + spf - step)
+        return n
+
     def _sway_offset(self, t: float) -> float:
         amp, freq = float(self.mesh_sway[0]), float(self.mesh_sway[1])
         return amp / (2.0 * np.pi * freq) * (1.0 - np.cos(2.0 * np.pi * freq * t))   # integral of amp sin(2 pi f t)

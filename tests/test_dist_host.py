@@ -116,3 +116,102 @@ def test_device_side_quantile_cuts_match_np_quantile_to_a_bin():
         assert sum(sizes) == px.size and max(sizes) - min(sizes) <= 0.1 * px.size / world + 48   # (lattice columns are 24 vertices)
         assert all(np.array_equal(s.cuts, cuts) for s in shards)
     assert md.cuts_from_histogram(np.zeros(md.CUT_BINS, np.int64), 4, 2.0).size == 0
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_a_rank_that_owns_nothing_takes_part_in_the_cuts(world):
+    """A cube squeezed onto one x: every particle falls to the last rank, the others own no vertex and no traditional particle.
+    Such a rank still selects (nothing) from its state tensor and adds CUT_BINS zeros to the summed histogram of device_cuts()
+    (it used to raise a NameError there while the other ranks were inside the all-reduce)."""
+    import torch
+    from dataclasses import replace
+    sc = scenes.small_cube()
+    x = sc.x.copy()
+    x[:, 0] = x[0, 0]
+    sc = replace(sc, x=x)
+    shards = mdist.partition(sc, world)
+    owning = [sh for sh in shards if sh.own_e.size + sh.own_t.size + sh.own_v.size > 0]
+    assert len(owning) == 1 and (shards[0].own_e.size, shards[0].own_t.size, shards[0].own_v.size) == (0, 0, 0)
+    hists = {}
+    for sh in shards:
+        px = torch.as_tensor(sh.scene.x)                      # a CPU state tensor of that shard's size
+        assert px.shape[0] == sh.scene.n_particles
+        xs = mdist.owned_movable_x(sh, px)
+        h = mdist.slab_histogram(xs, sc.grid_lim)
+        assert h.shape == (mdist.CUT_BINS,) and h.dtype == torch.int64 and h.device == px.device
+        if sh is not owning[0]:
+            assert xs.numel() == 0 and not h.any()
+        hists[sh.rank] = h
+    alone = mdist.cuts_from_histogram(hists[owning[0].rank].numpy(), world, sc.grid_lim)
+    summed = mdist.cuts_from_histogram(sum(hists.values()).numpy(), world, sc.grid_lim)
+    assert alone.size == world - 1 and np.array_equal(alone, summed)
+
+
+def test_nothing_is_forgotten_at_a_re_partition():
+    """Every attribute of a ShardedSim is a declared field of exactly one of the two groups -- what repartition() takes from the
+    fresh build (PartitionState) and what it leaves alone (RunState) -- also after the body-pose cache and the held-particle
+    buffer have been set; and the module stores to no other attribute of one."""
+    import ast
+    import dataclasses
+    import inspect
+    import types
+    import torch
+    from dist_worker import _sway_garment
+    rebuilt = {f.name for f in dataclasses.fields(mdist.PartitionState)}
+    survives = {f.name for f in dataclasses.fields(mdist.RunState)}
+    declared = {f.name for f in dataclasses.fields(mdist.ShardedSim)}
+    assert not (rebuilt & survives) and (rebuilt | survives) == declared
+    assert {"shard", "sim", "peers", "static", "since", "resort_now", "sorted_once", "halo_ref", "mass_version", "body_pose", "held_buf",
+            "global_scene", "transport"} <= rebuilt
+    assert {"steps_done", "resorts", "migrations", "trad_migrations", "trad_migrated", "trad_migration_ms", "migrate_fraction",
+            "migrate_halo_factor", "migrate_trad_fraction", "migrate_check_every", "migrate_checked_at"} <= survives
+    sc = _sway_garment()
+    sim = types.SimpleNamespace(mesh_x0=torch.zeros(1, 3), mesh_v=torch.zeros(1, 3), joint_verts_v=None, joint_faces_v=None,
+                                solver=types.SimpleNamespace(device="cpu"))
+    ss = mdist.ShardedSim(mdist.partition(sc, 2)[0], sim, "gloo", 0, global_scene=sc)
+    pose = mdist._body_at(ss, 25)                             # (frames of 20 substeps: the second frame's pose)
+    assert ss.body_pose.frame == 20 and mdist._body_at(ss, 39) is pose and mdist._body_at(ss, 40) is not pose
+    ss.held_buf = torch.zeros(1, 3)
+    assert set(vars(ss)) == declared
+    stored = {n.attr for n in ast.walk(ast.parse(inspect.getsource(mdist))) if isinstance(n, ast.Attribute)
+              and isinstance(n.ctx, ast.Store) and isinstance(n.value, ast.Name) and n.value.id in ("ss", "new")}
+    assert stored and stored <= declared, stored - declared
+
+
+def test_fused_run_lengths():
+    """Scene.fused_run: the runs from step 0 tile [0, N) exactly, and inside each the held count and the body's frame are constant;
+    with a shard's own share of the held particles as the count, the boundaries are those of the rule the sharded driver's in-library
+    loop carried inline."""
+    from dist_worker import _sway_garment
+
+    def inline_rule(gsc, held, step, n):
+        h = held(step)
+        if h >= 0:
+            n = next((j for j in range(1, n) if held(step + j) != h), n)
+        if gsc.mesh_sway is not None:
+            f0, spf = gsc.frame_of(step)
+            n = min(n, f0 + spf - step)
+        return n
+
+    def runs(rule, n_total):
+        out, k = [], 0
+        while k < n_total:
+            n = rule(k, n_total - k)
+            assert 1 <= n <= n_total - k
+            out.append((k, n))
+            k += n
+        assert k == n_total
+        return out
+    N = 237
+    for sc in (scenes.demo_mix(n_grid=48, n_sheet=16, sand=(16, 3, 8), hold=(10, 5, 64)), _sway_garment()):
+        segs = runs(sc.fused_run, N)
+        assert len(segs) > 1
+        for k0, n in segs:
+            assert len({(sc.joint_t_count(k), sc.frame_of(k)[0]) for k in range(k0, k0 + n)}) == 1
+        for k0, n in segs[:-1]:                               # ... and no run stops early
+            assert (sc.joint_t_count(k0 + n), sc.frame_of(k0 + n)[0]) != (sc.joint_t_count(k0), sc.frame_of(k0)[0])
+        for world in (2, 3):
+            for sh in mdist.partition(sc, world):
+                ss = type("S", (), {"global_scene": sc, "shard": sh})()
+                held = lambda step: mdist._held_local(ss, step)
+                assert runs(lambda k, n: sc.fused_run(k, n, count=held), N) == runs(lambda k, n: inline_rule(sc, held, k, n), N)

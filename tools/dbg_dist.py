@@ -9,7 +9,7 @@ sc = scenes.small_garment()
 P = lambda *a: print(f"[{rank}]", *a, flush=True)
 ss = mdist.build_sharded(sc, "cuda:0", rank, world, rebin_interval=8)
 torch.cuda.synchronize(); P("built", ss.shard.scene.n_particles)
-mdist.rebin_all(ss); torch.cuda.synchronize(); P("rebin ok, peers", [(p['rank'], p['n_halo'], p['n_gs'], p['n_gr']) for p in ss.peers])
+mdist.rebin_all(ss); torch.cuda.synchronize(); P("rebin ok, peers", [(p.rank, p.n_halo, p.ghosts.n_send if p.ghosts else 0, p.ghosts.n_recv if p.ghosts else 0) for p in ss.peers])
 sv = ss.sim.solver; sim = ss.sim
 dp = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
 sv._call("mpmhip_dist_step_begin", float(sc.dt), dp(sim.mesh_x0), dp(sim.mesh_v), 0.0, None, 0, dp(sim.joint_verts_v) or sv._dummy_ptr(), dp(sim.joint_faces_v) or sv._dummy_ptr())
