@@ -2,7 +2,8 @@
 
 Independent of ``mpm_oracle.c``: it uses convention-free closed forms (Gram-Schmidt QR with
 q3 = q1 x q2, closed-form 2x2 polar rotation, LAPACK SVD) instead of restating Warp's qr3/svd3 +
-sign flips, and float64 throughout.  Agreement between the two (tests/test_oracle_twin.py) was what
+sign flips, and float64 throughout.  The per-particle constitutive update (every traditional material and
+cloth) is tests/constitutive_ref.py, which its own fixture pins to the reference's source.  Agreement between the two (tests/test_oracle_twin.py) was what
 pinned the fp32 C oracle in round 1; since round 2 the reference's own kernel bodies, run over a NumPy stand-in of the warp module,
 pin it (mpm_oracle.h, PINNING) and the twin is the second, convention-free witness.
 It also generates the committed golden fixtures (tests/golden/make_golden.py).
@@ -13,8 +14,16 @@ cloth :101-209; isotropic models :8-84, :362-399, :1017-1105; colliders mpm_solv
 from __future__ import annotations
 
 import math
+import os
+import sys
 
 import numpy as np
+
+# the float64 restatement of the constitutive update lives with the tests that pin it (tests/constitutive_ref.py)
+_TESTS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests")
+if _TESTS not in sys.path:
+    sys.path.insert(0, _TESTS)
+import constitutive_ref as cref  # noqa: E402
 
 MATERIALS = {"jelly": 0, "metal": 1, "sand": 2, "foam": 3, "snow": 4, "plasticine": 5, "neo-hookean": 6, "cloth": 7}
 
@@ -85,6 +94,11 @@ class TwinMPM:
         self.mu = np.full(self.n_p, np.float64(E / (np.float32(2) * (np.float32(1) + nu))))
         self.lam = np.full(self.n_p, np.float64(E * nu / ((np.float32(1) + nu) * (np.float32(1) - np.float32(2) * nu))))
         self.gamma, self.kappa = float(sc.gamma), float(sc.kappa)
+        self.gamma_p, self.kappa_p = np.full(self.n_p, self.gamma), np.full(self.n_p, self.kappa)
+        f4 = lambda k, default: float(np.float32(p.get(k, default)))
+        self.ys = np.full(self.n_p, f4("yield_stress", 0.0))
+        self.hardening, self.xi = f4("hardening", 0.0), f4("xi", 0.0)            # init_other_params defaults,
+        self.plastic_viscosity, self.softening = f4("plastic_viscosity", 0.0), f4("softening", 0.1)   # mpm_data_structure.py:699-715
         ang = p.get("friction_angle", 0.0)
         sin_phi = math.sin(ang / 180.0 * 3.14159265)
         self.friction_coeff = float(np.float32(math.tan(ang / 180.0 * 3.14159265)))
@@ -98,6 +112,7 @@ class TwinMPM:
         self.njv, self.njf = sc.num_joint_v, sc.num_joint_f
         self.bcs = [(k, dict(v)) for k, v in sc.bcs]   # own copies: a moving cuboid updates its point
         self.time = 0.0
+        self.n_returned = 0
         G3 = self.G ** 3
         self.grid_m = np.zeros(G3)
         self.grid_v_in = np.zeros((G3, 3))
@@ -118,99 +133,33 @@ class TwinMPM:
         return np.stack([dw[:, 0, i] * w[:, 1, j] * w[:, 2, k], w[:, 0, i] * dw[:, 1, j] * w[:, 2, k],
                          w[:, 0, i] * w[:, 1, j] * dw[:, 2, k]], -1) * self.inv_dx  # [n,27,3]
 
-    # ------------------------------------------------------------------ constitutive
+    # ------------------------------------------------------------------ constitutive (tests/constitutive_ref.py)
     def cloth_return_mapping(self):
-        d = self.d
-        Q, R = qr_gs(d)
-        R = R.copy()
-        r22 = R[:, 2, 2].copy()
-        over = r22 > 1.0
-        fn = self.kappa * (1.0 - r22) ** 2
-        ff = self.gamma * np.sqrt(R[:, 0, 2] ** 2 + R[:, 1, 2] ** 2)
-        slide = (~over) & (ff > self.friction_coeff * fn)
-        scale = np.where(slide, self.friction_coeff * fn / np.where(ff > 0, ff, 1.0), 1.0)
-        R[:, 0, 2] *= scale
-        R[:, 1, 2] *= scale
-        R[over, 2, 2] = 1.0
-        d3 = np.einsum("nij,nj->ni", Q, R[:, :, 2])
-        nd = d.copy()
-        nd[:, :, 2] = d3
-        self.d = nd
+        n_e = self.n_e
+        self.d, _, _ = cref.cloth_return_map(self.d, self.gamma_p[:n_e], self.kappa_p[:n_e], self.friction_coeff)
 
     def cloth_stress(self):
-        d, n_e = self.d, self.n_e
-        iD11, iD12, iD22 = self.R_inv[:, 0], self.R_inv[:, 1], self.R_inv[:, 2]
-        mu, lam = self.mu[:n_e], self.lam[:n_e]
-        Q, R = qr_gs(d)
-        F11 = R[:, 0, 0] * iD11
-        F12 = R[:, 0, 0] * iD12 + R[:, 0, 1] * iD22
-        F22 = R[:, 1, 1] * iD22
-        th = np.arctan2(-F12, F11 + F22)  # polar rotation of [[F11,F12],[0,F22]]
-        c, s = np.cos(th), np.sin(th)
-        Rot = np.stack([np.stack([c, -s], -1), np.stack([s, c], -1)], -2)
-        F2 = np.zeros((n_e, 2, 2)); F2[:, 0, 0] = F11; F2[:, 0, 1] = F12; F2[:, 1, 1] = F22
-        iFTJ = np.zeros((n_e, 2, 2)); iFTJ[:, 0, 0] = F22; iFTJ[:, 1, 0] = -F12; iFTJ[:, 1, 1] = F11
-        J = F11 * F22
-        K2 = 2.0 * mu[:, None, None] * (F2 - Rot) + (lam * (J - 1.0))[:, None, None] * iFTJ
-        dr = np.zeros((n_e, 3, 3))
-        dr[:, 0, 0], dr[:, 0, 1], dr[:, 1, 1] = K2[:, 0, 0], K2[:, 0, 1], K2[:, 1, 1]
-        dr[:, 0, 2], dr[:, 1, 2] = self.gamma * R[:, 0, 2], self.gamma * R[:, 1, 2]
-        dr[:, 2, 2] = np.where(R[:, 2, 2] > 1.0, 0.0, -self.kappa * (1.0 - R[:, 2, 2]) ** 2)
-        RiDT = np.zeros((n_e, 3, 3))
-        RiDT[:, 0, 0] = F11; RiDT[:, 1, 0] = F12; RiDT[:, 1, 1] = F22
-        RiDT[:, 2, 0], RiDT[:, 2, 1], RiDT[:, 2, 2] = R[:, 0, 2], R[:, 1, 2], R[:, 2, 2]
-        K3 = dr @ RiDT
-        K3s = np.triu(K3) + np.transpose(np.triu(K3, 1), (0, 2, 1))
-        P = Q @ K3s @ np.linalg.inv(RiDT)
-        vol = self.vol[:n_e]
-        f2 = -vol[:, None] * (iD11[:, None] * P[:, :, 0] + iD12[:, None] * P[:, :, 1])
-        f3 = -vol[:, None] * iD22[:, None] * P[:, :, 1]
-        f1 = -(f2 + f3)
+        """Stress and vertex forces of the directors as they stand (their own QR, as the reference takes it again, mpm_utils.py:111)."""
+        n_e = self.n_e
+        Q, R = cref.qr_closed(self.d)
+        S, f1, f2, f3 = cref.cloth_stress(self.d, Q, R, self.R_inv, self.vol[:n_e], self.mu[:n_e], self.lam[:n_e],
+                                          self.gamma_p[:n_e], self.kappa_p[:n_e])
         vf = np.zeros((self.n_v, 3))
         np.add.at(vf, self.faces[:, 0], f1)
         np.add.at(vf, self.faces[:, 1], f2)
         np.add.at(vf, self.faces[:, 2], f3)
         self.vertex_force = vf
-        self.stress[:n_e] = vol[:, None, None] * np.einsum("ni,nj->nij", P[:, :, 2], d[:, :, 2])
+        self.stress[:n_e] = S
 
-    def trad_stress(self):
+    def trad_stress(self, dt):
+        """dt: the viscoplastic map is the only part of the update that reads it.  n_returned counts the particles whose
+        return map changed F, summed over the calls."""
         sl = slice(self.n_e, self.n_nv)
-        Ft = self.F_trial[sl]
-        mu, lam = self.mu[sl], self.lam[sl]
-        m = self.material
-        if m == 2:  # sand_return_mapping
-            U, s, Vt = np.linalg.svd(Ft)
-            eps = np.log(np.maximum(np.abs(s), 1e-14))
-            tr = eps.sum(-1)
-            eh = eps - tr[:, None] / 3.0
-            ehn = np.linalg.norm(eh, axis=-1)
-            dg = ehn + (3.0 * lam + 2.0 * mu) / (2.0 * mu) * tr * self.alpha
-            F = Ft.copy()
-            a = (dg > 0) & (tr > 0)
-            F[a] = (U @ Vt)[a]
-            b = (dg > 0) & (tr <= 0)
-            H = eps - eh * (dg / np.where(ehn > 0, ehn, 1.0))[:, None]
-            Fb = np.einsum("nij,nj,njk->nik", U, np.exp(H), Vt)
-            F[b] = Fb[b]
-        elif m in (1, 3, 5):
-            raise NotImplementedError("twin covers jelly / sand / cloth; plastic metals are pinned by KATs")
-        else:
-            F = Ft.copy()
-        self.F[sl] = F
-        J = np.linalg.det(F)
-        U, s, Vt = np.linalg.svd(F)
-        # proper rotations; for det F > 0 this is the polar rotation
-        Rm = U @ Vt
-        S = np.zeros_like(F)
-        FT = np.transpose(F, (0, 2, 1))
-        if m in (0, 5):
-            S = 2.0 * mu[:, None, None] * ((F - Rm) @ FT) + (lam * J * (J - 1.0))[:, None, None] * np.eye(3)
-        elif m == 2:
-            ls = np.log(s).sum(-1)
-            c = (2.0 * mu[:, None] * np.log(s) + lam[:, None] * ls[:, None]) / s
-            S = np.einsum("nij,nj,njk->nik", U, c, Vt) @ FT
-        S = 0.5 * (S + np.transpose(S, (0, 2, 1)))
-        self.stress[sl] = S
+        info = {}
+        self.F[sl], self.stress[sl], self.mu[sl], self.lam[sl], self.ys[sl] = cref.trad_update(
+            self.F_trial[sl], self.material, self.mu[sl], self.lam[sl], self.ys[sl], self.alpha, self.hardening, self.xi,
+            self.plastic_viscosity, self.softening, dt, info)
+        self.n_returned += int(np.sum(info.get("changed", 0)))
 
     # ------------------------------------------------------------------ transfers
     def p2g(self, dt):
@@ -370,7 +319,7 @@ class TwinMPM:
         else:
             self.vertex_force = np.zeros((self.n_v, 3))
         if self.n_t:
-            self.trad_stress()
+            self.trad_stress(dt)
         self.p2g(dt)
         self.grid_update(dt)
         if self.has_collider:

@@ -18,6 +18,8 @@ line that runs is the reference's.  Two kinds of fixture:
                         grid_normalization_and_gravity, add_damping_via_grid, the mesh collider's four kernels, the
                         particle mover's five, every grid BC, the pre-p2g particle operations, g2p_v, g2p_e)
   ref_seq_<case>.npz    whole-substep sequences (tens of substeps) of the small test scenes, state at checkpoints
+  ref_edge_constitutive.npz   compute_stress_from_F_trial alone on the edge table of tests/constitutive_ref.py (every traditional
+                        material and cloth, at the shapes and thresholds where the update branches): inputs and outputs
 
 Only data is written (inputs + the reference's outputs); nothing of the reference travels.  ``svd3`` / ``qr3`` are the
 stand-in's (Warp's are out of tree): every trace fixture is generated under BOTH SVD and BOTH QR conventions of the
@@ -455,8 +457,78 @@ def make_cov_from_F(name="ref_cov_from_F"):
     save(name, {"particle_F_trial": F_trial, "particle_cov": cov0, "new_cov": new_cov})
 
 
+def make_edge_constitutive(name="ref_edge_constitutive", count=8):
+    """The reference's compute_stress_from_F_trial (mpm_utils.py:1017-1105), unchanged, on the edge table of
+    tests/constitutive_ref.py: once per traditional material, once on the inverted sand states (non-finite stress, host-side
+    tests only) and twice for cloth (friction coefficient of the model at 40 degrees and at zero).  Inputs and outputs only.
+    `count` cases per family -- tests/test_constitutive_edges.py::FIXTURE_COUNT."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import constitutive_ref as cr
+    from mpm_utils import compute_stress_from_F_trial
+    wp.SVD_MODE, wp.QR_MODE = "lapack", "householder"
+    payload = {}
+
+    def trad_once(tag, material, tab):
+        n = tab["F_trial"].shape[0]
+        params = {"material": material, "g": [0.0, 0.0, 0.0], "hardening": tab["hardening"], "xi": tab["xi"],
+                  "plastic_viscosity": tab["plastic_viscosity"], "softening": tab["softening"]}
+        if material == "sand":
+            params["friction_angle"] = cr.TRAD_PARAMS["friction_angle"]
+        sim = build_reference(scenes._trad_scene(f"edge-{tag}", cr.lattice(n), 0.02 ** 3, 8, material=material, params=params))
+        assert abs(float(sim.model.alpha) - tab["alpha"]) <= 1e-7 * max(tab["alpha"], 1.0), (sim.model.alpha, tab["alpha"])
+        sim.state.particle_F_trial.numpy()[...] = tab["F_trial"]
+        for f, k in (("mu", "mu"), ("lam", "lam"), ("yield_stress", "ys")):
+            getattr(sim.model, f).numpy()[...] = tab[k]
+        wp.launch(kernel=compute_stress_from_F_trial, dim=n, inputs=[sim.state, sim.model, tab["dt"]], device="cpu")
+        out = {f: getattr(sim.state, f).numpy().copy() for f in ("particle_F", "particle_stress")}
+        out.update({f: getattr(sim.model, f).numpy().copy() for f in MODEL_FIELDS})
+        return out
+
+    def trad(tag, material, tab):
+        """SVD_MODE "lapack"; the states with det F < 0 under "rot" -- proper U and V, the sign in the last singular value, which
+        is what Warp's svd3 returns and what decides their result (the polar factor of the jelly, the log of the sand).  Every
+        other row must not depend on the choice."""
+        wp.SVD_MODE = "lapack"
+        out = trad_once(tag, material, tab)
+        wp.SVD_MODE = "rot"
+        alt = trad_once(tag, material, tab)
+        wp.SVD_MODE = "lapack"
+        inv = np.linalg.det(tab["F_trial"].astype(np.float64)) < 0
+        for f in out:
+            a, b = out[f][~inv].astype(np.float64), alt[f][~inv].astype(np.float64)
+            if a.size:
+                assert np.abs(a - b).max() <= 2e-6 * max(np.abs(a).max(), 1e-3), (tag, f, np.abs(a - b).max())
+            out[f][inv] = alt[f][inv]
+            payload[f"{tag}_{f}"] = out[f]
+        for k in ("F_trial", "mu", "lam", "ys"):
+            payload[f"{tag}_in_{k}"] = tab[k]
+
+    for material in cr.TRAD_MATERIALS:
+        trad(material, material, cr.trad_table(material, count=count))
+    trad("sand_inverted", "sand", cr.trad_table("sand", count=count, host_only=True))
+    for tag, fc in (("cloth", None), ("cloth_fc0", 0.0)):
+        tab = cr.cloth_table(count=count, friction_coeff=fc)
+        n = tab["d"].shape[0]
+        x = np.concatenate([tab["verts"].mean(1), tab["verts"].reshape(-1, 3)], 0).astype(np.float32)
+        sc = scenes.Scene(name=f"edge-{tag}", n_grid=8, grid_lim=2.0, n_elements=n, n_traditional=0, n_vertices=3 * n, x=x,
+                          v=np.zeros_like(x), vol=np.concatenate([tab["vol"], np.repeat(tab["vol"], 3)]).astype(np.float32),
+                          faces=np.arange(3 * n, dtype=np.int32).reshape(n, 3), d=tab["d"], R_inv=tab["R_inv"],
+                          params={"material": "cloth", "g": [0.0, 0.0, 0.0], "friction_angle": 0.0 if fc == 0.0 else cr.TRAD_PARAMS["friction_angle"]})
+        sim = build_reference(sc)
+        assert abs(float(sim.model.friction_coeff) - tab["friction_coeff"]) <= 1e-7, (sim.model.friction_coeff, tab["friction_coeff"])
+        for k in ("mu", "lam", "gamma", "kappa"):
+            getattr(sim.model, k).numpy()[:n] = tab[k]
+        for k in ("d", "R_inv", "vol", "mu", "lam", "gamma", "kappa"):
+            payload[f"{tag}_in_{k}"] = tab[k]
+        wp.launch(kernel=compute_stress_from_F_trial, dim=n, inputs=[sim.state, sim.model, 1e-6], device="cpu")
+        for f in ("particle_d", "particle_stress", "vertex_force"):
+            payload[f"{tag}_{f}"] = getattr(sim.state, f).numpy().copy()
+    save(name, payload)
+
+
 FIXTURES = {
     "ref_cov_from_F": make_cov_from_F,
+    "ref_edge_constitutive": make_edge_constitutive,
     # --- per-kernel traces from random states
     **{f"ref_trace_{m}": (lambda m=m, i=i: make_trace(f"ref_trace_{m}", *trace_scene_traditional(m, 100 + i), with_pre=(m == "jelly")))
        for i, m in enumerate(["jelly", "metal", "sand", "foam", "snow", "plasticine"])},

@@ -72,3 +72,13 @@ extern "C" void hm_qr(const float *d, float *Q, float *R) {  // Q, R row-major, 
   float r[9] = {q.r00, q.r01, q.r02, 0.f, q.r11, q.r12, 0.f, 0.f, q.r22};
   memcpy(R, r, sizeof r);
 }
+
+// svd3 on n matrices (row-major A, U, V; sig as svd3 returns it: the sign of det A in sig[2])
+extern "C" void hm_svd(const float *A, int n, float *U, float *sig, float *V) {
+  for (int i = 0; i < n; ++i) {
+    M3 u, v;
+    V3 s;
+    svd3(load_m3(A + 9 * i), u, s, v);
+    store_m3(U + 9 * i, u); store_v3(sig + 3 * i, s); store_m3(V + 9 * i, v);
+  }
+}

@@ -4,9 +4,13 @@ mpm_math.hpp is plain per-particle C++ (no memory traffic); compiled with g++ ov
 <hip/hip_runtime.h> it runs on the host.  The oracle's test hooks (oracle/mpm_oracle.c: orc_hook_element /
 orc_hook_traditional) let it take the place of the oracle's own constitutive restatement inside the oracle's substep, so
 the ARITHMETIC THE GPU KERNELS USE -- QR, return mappings, Kirchhoff stresses, the Jacobi SVD -- is checked here, without
-a GPU, against sequences the reference's own source produced (tests/golden/ref_seq_*.npz).  What this cannot see: FMA
-contraction as hipcc applies it (the host build is contraction-free, like the oracle; a second build with g++'s
-contraction on brackets it) and v_rcp / v_rsq being 1-ulp approximations on the device.
+a GPU, against sequences the reference's own source produced (tests/golden/ref_seq_*.npz).  Those sequences start from rest
+and stay near well-conditioned states; the same host builds are held to float64, function by function (svd3 itself
+included), at the shapes and thresholds where the update branches by tests/test_constitutive_edges.py.  What no host build
+can see: FMA contraction as hipcc applies it (the host build is contraction-free, like the oracle; a second build with
+g++'s contraction on brackets it), v_rcp / v_rsq being 1-ulp approximations on the device, and the wave-wide vote that ends
+svd3's sweep loop (the stub's __any has one lane) -- tests/test_gpu_constitutive_edges.py runs the same edge table through
+the kernels for those.
 
 This is the test that found the round-1/2 Gram-Schmidt QR (q2 = q0 x q1, not re-normalised) to be biased at the r22 = 1
 discontinuity of the cloth return mapping (mpm_utils.py:196-204): 2.7x further from the reference than the Givens QR of

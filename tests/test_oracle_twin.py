@@ -31,6 +31,39 @@ def test_cube_100_substeps(material, params, oracle_lib):
     assert rel(o.x, t.x) < 1e-5 and rel(o.v, t.v) < 2e-4 and rel(o.F_trial, t.F_trial) < 1e-5
 
 
+# The spinning cube strains itself to |dev tau| <= 0.035: yield stresses just under that put part of it through the return maps
+# (measured: 2 % / 3 % / 0.4 % of all particle-substeps for metal / foam / plasticine, 14 % of the particles; 13 % of the plasticine ends with mu = lam = 0).
+PLASTIC = [("metal", {"yield_stress": 0.025, "hardening": 1, "xi": 0.1}),
+           ("foam", {"yield_stress": 0.03, "plastic_viscosity": 0.01}),
+           ("plasticine", {"yield_stress": 0.025, "hardening": 1, "xi": 0.1, "softening": 300.0})]
+
+
+@pytest.mark.parametrize("material,params", PLASTIC)
+def test_plastic_cube_100_substeps(material, params, oracle_lib):
+    """Hardening, viscoplastic flow and damage softening at the bounds of the elastic cube -- and they must have happened."""
+    sc = scenes.small_cube(material=material, params=params)
+    o, t = pair(sc, 100)
+    assert rel(o.x, t.x) < 1e-5 and rel(o.v, t.v) < 2e-4 and rel(o.F_trial, t.F_trial) < 1e-5
+    n, ys0 = sc.n_traditional, np.float32(params["yield_stress"])
+    returned = t.n_returned / (100.0 * n)
+    print(f"{material}: {returned:.4f} of the particle-substeps went through the return map; ys changed on "
+          f"{(t.ys != ys0).mean():.2f} / {(o.yield_stress != ys0).mean():.2f} of the particles (twin / oracle); "
+          f"mu = 0 on {(t.mu == 0).mean():.2f} / {(o.mu == 0).mean():.2f}")
+    assert returned > {"metal": 0.01, "foam": 0.015, "plasticine": 0.002}[material]
+    if material == "foam":
+        assert (t.ys == ys0).all() and (o.yield_stress == ys0).all()      # the viscoplastic map leaves ys alone
+    else:
+        assert (t.ys != ys0).mean() > 0.1 and (o.yield_stress != ys0).mean() > 0.1     # measured 0.14, both
+        sign = 1 if material == "metal" else -1                           # hardening raises ys; softening at 300 outweighs it
+        assert (sign * (t.ys[t.ys != ys0] - ys0) > 0).all()
+    if material == "plasticine":
+        dead_t, dead_o = t.mu == 0, o.mu == 0
+        assert dead_t.mean() > 0.05 and dead_o.mean() > 0.05 and (dead_t != dead_o).mean() < 0.01
+        assert (t.lam[dead_t] == 0).all() and (t.ys[dead_t] <= 0).all()
+    else:
+        assert (t.mu > 0).all() and (o.mu > 0).all()
+
+
 @pytest.mark.parametrize("params", [{"rpic_damping": 0.3}, {"rpic_damping": -1.0}, {"grid_v_damping_scale": 0.9},
                                     {"rpic_damping": 0.5, "grid_v_damping_scale": 0.97}])
 def test_rpic_and_grid_damping(params, oracle_lib):
