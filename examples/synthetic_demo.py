@@ -6,7 +6,10 @@ end on one MI355X, minus the two third-party stages (Blender AO bake, diff_gauss
                 -> read back the cloth vertices -> uvmesh/NNN.obj (+ sand/NNN.obj)
                 -> per-face frames -> world-space parameters of the Gaussians bound to the faces (on the device)
 
-    python examples/synthetic_demo.py --out /tmp/demo --frames 5 --substeps 400 [--scene demo-mix|garment]
+    python examples/synthetic_demo.py --out /tmp/demo --frames 5 --substeps 400 [--scene demo-mix|garment] [--geo-metrics]
+
+--geo-metrics adds the geometry loop of eval.py:30-56 on the device (mpmavatar_amd/geo_metrics.py): Chamfer distance and F-score
+of every frame's mesh against the rest mesh (the stand-in for the dataset's ground-truth meshes), written to geo_metric.npz.
 """
 import argparse
 import os
@@ -28,6 +31,7 @@ def main(argv=None):
     ap.add_argument("--substeps", type=int, default=400)
     ap.add_argument("--scene", default="demo-mix", choices=["demo-mix", "garment"])
     ap.add_argument("--gaussians-per-face", type=int, default=4)
+    ap.add_argument("--geo-metrics", action="store_true")
     a = ap.parse_args(argv)
     sc = scenes.demo_mix() if a.scene == "demo-mix" else scenes.small_garment()
     sim = harness.build_solver(sc, "cuda:0")
@@ -48,6 +52,10 @@ def main(argv=None):
     _xyz = 0.3 * torch.randn(n_g, 3, device=dev, generator=g)
     _rot = torch.randn(n_g, 4, device=dev, generator=g)
     _scl = -3.0 + 0.3 * torch.randn(n_g, 3, device=dev, generator=g)
+    geo = rest = None
+    if a.geo_metrics:
+        from mpmavatar_amd.geo_metrics import GeoEval
+        geo, rest = GeoEval(faces), sim.state.particle_x[ne + nt:].clone()
     t_sim = t_io = 0.0
     for frame in range(a.frames):
         t0 = time.perf_counter()
@@ -58,6 +66,8 @@ def main(argv=None):
         verts = pos[ne + nt:].contiguous()
         frames.set_mesh_by_verts(verts)
         xyz, rot, scale = frames.get_all(binding, _xyz, _rot, _scl)
+        if geo:
+            geo.add_frame(verts, rest, faces)
         writer.write(os.path.join(a.out, "uvmesh"), frame + 1, verts.cpu().numpy())
         if nt:
             io_formats.write_points_obj(os.path.join(a.out, "sand"), frame + 1, pos[ne:ne + nt].cpu().numpy())
@@ -68,6 +78,10 @@ def main(argv=None):
     print(f"{a.frames} frames x {a.substeps} substeps of {sc.name}: simulation {1e3 * t_sim / a.frames:.1f} ms/frame "
           f"({a.frames * a.substeps / t_sim:.0f} substeps/s), frames + OBJ output {1e3 * t_io / a.frames:.1f} ms/frame; "
           f"{n_g} Gaussians bound to {sc.n_elements} faces; files under {a.out}")
+    if geo:
+        res = geo.results()
+        print(f"geometry against the rest mesh: CD {res['CD'].mean():.4f}, F-Score {res['F-Score'].mean():.2f} (means over the frames); "
+              f"{geo.save(a.out)}")
     return dict(xyz=xyz, rot=rot, scale=scale, verts=verts)
 
 

@@ -325,6 +325,40 @@ int mpmhip_render_inputs(int32_t device, void *stream, int32_t n_gaussians, int3
 int mpmhip_cov_from_F(int32_t device, void *stream, const float *particle_F_trial, const float *particle_cov, int32_t n,
                       float *new_cov);
 
+/* ---- after the solver: geometry evaluation --------------------------------------------------
+ * What every run of the reference ends with: eval.py:30-56 calls metric.all_mesh_metrics (metric.py:56-63) per frame --
+ * 100,000 area-weighted surface samples on each mesh (metric.py:4-8, trimesh's sample_surface), nearest neighbours in
+ * both directions (metric.py:18-21, SciPy's cKDTree there; exact brute force here), Chamfer distance (metric.py:23-32)
+ * and F-score at tau = 1e-3 (metric.py:34-54).  Stand-alone maps on [dev] arrays (no solver context; `stream` is a
+ * hipStream_t, NULL = default stream); nothing here allocates or synchronises, every buffer is the caller's.
+ * All four return MPMHIP_ERR_INVALID for a count <= 0, a NULL required pointer or slices < 0.
+ *
+ * mpmhip_face_areas: area [n_f] = 0.5 |(v1 - v0) x (v2 - v0)| in fp32.  The caller accumulates them (float64, inclusive)
+ * into area_cdf [n_f] for mpmhip_mesh_sample. */
+int mpmhip_face_areas(int32_t device, void *stream, const float *verts, const int32_t *faces, int32_t n_faces, float *area);
+/* metric.py:4-8 without the normals: uniforms [n_samples*3] in [0, 1); sample i lies on the first face f with
+ * area_cdf[f] >= (double)u0 * area_cdf[n_f-1] (numpy.searchsorted, side "left": zero-area faces are never picked) at
+ * v0 + u1 (v1 - v0) + u2 (v2 - v0), (u1, u2) folded back into the triangle when u1 + u2 > 1.
+ * points [n_samples*3]; face_index [n_samples] may be NULL. */
+int mpmhip_mesh_sample(int32_t device, void *stream, const float *verts, const int32_t *faces, int32_t n_faces,
+                       const double *area_cdf, const float *uniforms, int32_t n_samples, float *points,
+                       int32_t *face_index);
+/* metric.py:18-21 squared: dist2 [n_src] = min_j |src_i - dst_j|^2 in the direct form (within 8 * 2^-24 relative of the
+ * exact value), index [n_src] (may be NULL) the lowest j that attains it.  src [n_src*3], dst [n_dst*3].
+ * best_scratch [n_src] 64-bit words.  slices: in how many parts the targets are cut so that few queries still fill the
+ * device (0 = chosen from the sizes; larger than n_dst is clamped); the result does not depend on it, bit for bit.
+ * Non-finite coordinates give unspecified values, never an access outside the arrays. */
+int mpmhip_nn_dist2(int32_t device, void *stream, const float *src, int32_t n_src, const float *dst, int32_t n_dst,
+                    int32_t slices, uint64_t *best_scratch, float *dist2, int32_t *index);
+/* metric.py:31 and :34-41 from the two dist2 arrays: out [4] doubles on the device = F-score, Chamfer distance
+ * (1000 * (mean12 + mean21)), precision, recall (percent of dist2 <= tau: the reference compares the SQUARED distance
+ * with its threshold, metric.py:35).  Sums in fp64 in a fixed order (no floating-point atomics): bitwise reproducible.
+ * scratch [MPMHIP_GEO_REDUCE_SCRATCH] doubles.  No host synchronisation: the reference's .item() (eval.py:50-51) is the
+ * caller's choice. */
+#define MPMHIP_GEO_REDUCE_SCRATCH 256
+int mpmhip_geo_reduce(int32_t device, void *stream, const float *dist2_12, int32_t n1, const float *dist2_21, int32_t n2,
+                      double tau, double *scratch, double *out);
+
 /* ---- introspection ---------------------------------------------------------------------- */
 /* dense reference-layout copies of grid_m [G^3], grid_v_in [G^3*3], grid_v_out [G^3*3] as they
  * stand after the last substep's grid stage ([dev] outputs, any may be NULL).  Synchronous. */

@@ -93,6 +93,10 @@ SIGNATURES = {
     "mpmhip_face_frames": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, vp]),
     "mpmhip_bind_gaussians": (C.c_int, [C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "mpmhip_render_inputs": (C.c_int, [C.c_int32, vp, C.c_int32, C.c_int32] + [vp] * 18),
+    "mpmhip_face_areas": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, vp]),
+    "mpmhip_mesh_sample": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp]),
+    "mpmhip_nn_dist2": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp]),
+    "mpmhip_geo_reduce": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_double, vp, vp]),
     "mpmhip_dist_enable": (C.c_int, [vp]),
     "mpmhip_dist_set_ghost_mode": (C.c_int, [vp, C.c_int32]),
     "mpmhip_dist_set_mass_span": (C.c_int, [vp, C.c_float, C.c_float]),

@@ -112,3 +112,11 @@ def load_params(filename):
     p["loss"] = 1.0
     p["step"] = -1
     return p
+
+
+def write_geo_metric_npz(directory, chamfer, fscore):
+    """geo_metric.npz of eval.py:31,56: one float64 value per frame under the keys "CD" and "F-Score"."""
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, "geo_metric.npz")
+    np.savez(path, **{"CD": np.asarray(chamfer, np.float64), "F-Score": np.asarray(fscore, np.float64)})
+    return path
