@@ -359,6 +359,63 @@ int mpmhip_nn_dist2(int32_t device, void *stream, const float *src, int32_t n_sr
 int mpmhip_geo_reduce(int32_t device, void *stream, const float *dist2_12, int32_t n1, const float *dist2_21, int32_t n2,
                       double tau, double *scratch, double *out);
 
+/* ---- after the solver: the forward Gaussian rasteriser --------------------------------------------------------------
+ * What the reference calls as diff_gauss.GaussianRasterizer (gaussian_renderer/__init__.py:14,36-103; the extension is not
+ * vendored there, README.md:51): the published 3D Gaussian splatting forward pass, forward only, as the eval loop
+ * (train_material_params.py:857-872) and the demo (run_demo.py:540-604) use it.  All arithmetic fp32, no floating-point
+ * atomics: the same input gives the same bits.
+ *
+ * GaussianRasterizationSettings, gaussian_renderer/__init__.py:36-49 (prefiltered and debug have no meaning here).
+ * viewmatrix / projmatrix are the reference's world_view_transform / full_proj_transform (scene/cameras.py:26-39): row-major,
+ * points multiply from the left as row vectors. */
+typedef struct {
+  int32_t image_height, image_width;
+  float tanfovx, tanfovy;
+  float bg[3];
+  float scale_modifier;
+  int32_t sh_degree;       /* 0..3, read only when shs is given */
+  const float *viewmatrix; /* [dev] [16] */
+  const float *projmatrix; /* [dev] [16] */
+  const float *campos;     /* [dev] [3] */
+} mpmhip_raster_settings;
+
+/* of the newest mpmhip_raster_forward of a handle */
+typedef struct {
+  int64_t n_entries;        /* (tile, Gaussian) pairs that were sorted */
+  int32_t max_tile_entries; /* the longest tile list */
+  int32_t n_visible;        /* Gaussians with radius > 0 */
+  int64_t scratch_bytes;    /* device memory the handle holds */
+} mpmhip_raster_stats_t;
+
+typedef struct mpmhip_raster mpmhip_raster;
+
+/* A handle owns the scratch of the pipeline (records, sort keys, sort temporaries, tile ranges) on `device` and launches on
+ * `stream` (hipStream_t, NULL = default stream).  The scratch grows geometrically when a frame needs more and is reused
+ * otherwise: no allocation in steady state.  Not thread-safe; distinct handles are independent. */
+int mpmhip_raster_create(int32_t device, void *stream, mpmhip_raster **out);
+void mpmhip_raster_destroy(mpmhip_raster *r);
+/* The rasterizer(...) call of gaussian_renderer/__init__.py:95-103 on [dev] arrays: means3D [n*3]; shs [n*n_sh_coeffs*3]
+ * (coefficient-major, GaussianModel.get_features) evaluated as utils/sh_utils.py:57-100 does at degree sh_degree, OR
+ * colors_precomp [n*3]; opacities [n]; scales [n*3] and rotations [n*4] WXYZ, OR cov3D_precomp [n*6] (xx xy xz yy yz zz).
+ * Outputs: out_color [3*H*W] (= colour + T * bg), out_alpha [H*W] (= 1 - T, the reference's mask), radii [n] (0 = culled).
+ * Blocks the host once per call: the number of (tile, Gaussian) entries is read back to size the sort, as in the CUDA
+ * original; everything else is asynchronous on the handle's stream.
+ * MPMHIP_ERR_INVALID: n < 0, a non-positive image size, both or neither of shs / colors_precomp, both or neither of
+ * (scales, rotations) / cov3D_precomp, sh_degree outside 0..3 or n_sh_coeffs < (sh_degree + 1)^2; nothing is launched then.
+ * n == 0 renders the background.  MPMHIP_ERR_LIMIT: more than 2^31 - 1 entries. */
+int mpmhip_raster_forward(mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, const float *means3D, const float *shs,
+                          int32_t n_sh_coeffs, const float *colors_precomp, const float *opacities, const float *scales,
+                          const float *rotations, const float *cov3D_precomp, float *out_color, float *out_alpha,
+                          int32_t *radii);
+/* counts of the newest frame; synchronous, runs one small count kernel */
+int mpmhip_raster_stats(const mpmhip_raster *r, mpmhip_raster_stats_t *out);
+/* Measurement only (tools/raster_bench.py; the counterpart of mpmhip_profile_enable for this pipeline): while on, every
+ * frame is bracketed by hipEvents between its stages -- preprocess, scan + read-back, duplicate, sort, ranges, render -- and
+ * waits for its last one.  The call first copies out what was accumulated so far (stage_ms [MPMHIP_RASTER_STAGES] milliseconds
+ * summed over `frames` frames; either may be NULL); switching from off to on then resets the sums. */
+#define MPMHIP_RASTER_STAGES 6
+int mpmhip_raster_profile(mpmhip_raster *r, int32_t on, double *stage_ms, int64_t *frames);
+
 /* ---- introspection ---------------------------------------------------------------------- */
 /* dense reference-layout copies of grid_m [G^3], grid_v_in [G^3*3], grid_v_out [G^3*3] as they
  * stand after the last substep's grid stage ([dev] outputs, any may be NULL).  Synchronous. */

@@ -63,6 +63,16 @@ class DistPeer(C.Structure):
                 ("send_p", vp), ("recv_p", vp), ("send_e", vp), ("recv_e", vp), ("ghost_send", vp), ("ghost_recv", vp)]
 
 
+class RasterSettings(C.Structure):
+    _fields_ = [("image_height", C.c_int32), ("image_width", C.c_int32), ("tanfovx", C.c_float), ("tanfovy", C.c_float),
+                ("bg", f3), ("scale_modifier", C.c_float), ("sh_degree", C.c_int32), ("viewmatrix", vp), ("projmatrix", vp),
+                ("campos", vp)]
+
+
+class RasterStats(C.Structure):
+    _fields_ = [("n_entries", C.c_int64), ("max_tile_entries", C.c_int32), ("n_visible", C.c_int32), ("scratch_bytes", C.c_int64)]
+
+
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
 SIGNATURES = {
     "mpmhip_version": (C.c_int, []),
@@ -97,6 +107,11 @@ SIGNATURES = {
     "mpmhip_mesh_sample": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp]),
     "mpmhip_nn_dist2": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp]),
     "mpmhip_geo_reduce": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_double, vp, vp]),
+    "mpmhip_raster_create": (C.c_int, [C.c_int32, vp, C.POINTER(vp)]),
+    "mpmhip_raster_destroy": (None, [vp]),
+    "mpmhip_raster_forward": (C.c_int, [vp, C.POINTER(RasterSettings), C.c_int32, vp, vp, C.c_int32] + [vp] * 8),
+    "mpmhip_raster_stats": (C.c_int, [vp, C.POINTER(RasterStats)]),
+    "mpmhip_raster_profile": (C.c_int, [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "mpmhip_dist_enable": (C.c_int, [vp]),
     "mpmhip_dist_set_ghost_mode": (C.c_int, [vp, C.c_int32]),
     "mpmhip_dist_set_mass_span": (C.c_int, [vp, C.c_float, C.c_float]),

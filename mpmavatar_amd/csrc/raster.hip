@@ -1,0 +1,431 @@
+// raster.hip -- forward Gaussian rasteriser: what the reference calls as diff_gauss.GaussianRasterizer
+// (/root/reference/gaussian_renderer/__init__.py:14,36-103), forward only, as the eval loop
+// (train_material_params.py:857-872) and the demo (run_demo.py:540-604) use it.  The math is raster_math.hpp; this file is
+// the pipeline:
+//
+//   k_raster_preprocess  one lane per Gaussian: projection, conic, radius, tile rectangle, colour -> packed records
+//   rocprim::exclusive_scan of tiles_touched (n + 1 values: the last offset is the entry count)
+//   >> the entry count is read back with one 8-byte device-to-host copy: ONE STREAM SYNCHRONISATION PER RENDERED FRAME,
+//      as the CUDA original has (it sizes the sort).  Nothing in the solver path calls into this file.
+//   k_raster_duplicate   key (tile << 32 | depth bits) and Gaussian index for every (tile, Gaussian) entry
+//   rocprim::radix_sort_pairs over bits [0, 32 + ceil(log2 tiles)): stable, so equal depths keep the index order
+//   k_raster_ranges      start / end of every tile's run in the sorted keys
+//   k_raster_render      one workgroup of 256 lanes per 16 x 16 tile, front-to-back blend (the hot path)
+//
+// No floating-point atomics anywhere: the same input gives the same bits.  The scratch (records, keys, sort temporaries,
+// tile ranges) belongs to the handle, grows geometrically when a frame needs more and is reused otherwise: no allocation
+// in steady state.  Measured numbers: DESIGN.md section 13, profiles/raster_bench.json.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <new>
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include "../../include/mpmhip.h"
+#include "raster_math.hpp"
+
+struct mpmhip_raster {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  // per Gaussian (capacity cap_n)
+  int cap_n = 0;
+  float4 *rec0 = nullptr, *rec1 = nullptr;  // (px, py, opacity, depth), (A, B, C, 0)
+  float *colour = nullptr;                  // [n*3]
+  int4 *rect = nullptr;                     // x0 y0 x1 y1
+  uint32_t *touched = nullptr;              // [n + 1], the last one 0
+  uint64_t *offsets = nullptr;              // [n + 1] exclusive scan; offsets[n] = number of entries
+  void *scan_tmp = nullptr;
+  size_t scan_tmp_bytes = 0;
+  // per (tile, Gaussian) entry (capacity cap_e)
+  size_t cap_e = 0;
+  uint64_t *keys[2] = {nullptr, nullptr};
+  uint32_t *vals[2] = {nullptr, nullptr};
+  void *sort_tmp = nullptr;
+  size_t sort_tmp_bytes = 0;
+  // per tile (capacity cap_tiles)
+  int cap_tiles = 0;
+  uint2 *ranges = nullptr;
+  // small
+  uint64_t *h_total = nullptr;  // pinned
+  int32_t *d_counts = nullptr;  // [2]: longest tile list, Gaussians with radius > 0 (mpmhip_raster_stats)
+  // the last frame, for mpmhip_raster_stats
+  int64_t last_entries = 0;
+  int last_n = 0, last_tiles = 0;
+  // mpmhip_raster_profile: events between the stages of a frame (off by default: no events, no extra synchronisation)
+  bool profile = false;
+  hipEvent_t ev[MPMHIP_RASTER_STAGES + 1] = {};
+  double stage_ms[MPMHIP_RASTER_STAGES] = {};
+  int64_t profiled_frames = 0;
+};
+
+namespace {
+
+constexpr int TPB = 256;
+constexpr int TILE = rast::TILE;
+static_assert(TILE * TILE == TPB, "one lane per pixel of a tile");
+
+struct Camera {  // the scalar half of mpmhip_raster_settings plus its three device pointers
+  int W, H, gx, gy;
+  float tanfovx, tanfovy, scale_modifier;
+  int sh_degree;
+  const float *view, *proj, *campos;
+};
+
+__global__ __launch_bounds__(TPB) void k_raster_preprocess(int n, Camera cam, const float *__restrict__ means,
+                                                           const float *__restrict__ shs, int n_sh,
+                                                           const float *__restrict__ colors, const float *__restrict__ opac,
+                                                           const float *__restrict__ scales, const float *__restrict__ rots,
+                                                           const float *__restrict__ cov, float4 *rec0, float4 *rec1,
+                                                           float *colour, int4 *rect, uint32_t *touched, int32_t *radii) {
+  int i = blockIdx.x * TPB + threadIdx.x;
+  if (i > n) return;
+  if (i == n) { touched[n] = 0; return; }  // the scan runs over n + 1 values
+  float V[16], P[16];
+  for (int k = 0; k < 16; ++k) { V[k] = cam.view[k]; P[k] = cam.proj[k]; }
+  const size_t s = (size_t)i;
+  rast::V3 mean{means[3 * s], means[3 * s + 1], means[3 * s + 2]};
+  rast::Sym3 S;
+  if (cov) {
+    const float *c = cov + 6 * s;
+    S = rast::Sym3{c[0], c[1], c[2], c[3], c[4], c[5]};
+  } else {
+    S = rast::cov3d(rast::V3{scales[3 * s], scales[3 * s + 1], scales[3 * s + 2]}, cam.scale_modifier,
+                    rast::V4{rots[4 * s], rots[4 * s + 1], rots[4 * s + 2], rots[4 * s + 3]});
+  }
+  rast::Splat o = rast::project(mean, S, V, P, cam.W, cam.H, cam.tanfovx, cam.tanfovy, cam.gx, cam.gy);
+  radii[i] = o.radius;
+  if (o.radius == 0) {
+    touched[i] = 0;
+    rect[i] = make_int4(0, 0, 0, 0);
+    return;
+  }
+  rast::V3 col;
+  if (shs) col = rast::sh_colour(cam.sh_degree, shs + 3 * (size_t)n_sh * s, mean, rast::V3{cam.campos[0], cam.campos[1], cam.campos[2]});
+  else col = rast::V3{colors[3 * s], colors[3 * s + 1], colors[3 * s + 2]};
+  rec0[i] = make_float4(o.px, o.py, opac[i], o.depth);
+  rec1[i] = make_float4(o.A, o.B, o.C, 0.f);
+  colour[3 * s] = col.x; colour[3 * s + 1] = col.y; colour[3 * s + 2] = col.z;
+  rect[i] = make_int4(o.x0, o.y0, o.x1, o.y1);
+  touched[i] = (uint32_t)(o.x1 - o.x0) * (uint32_t)(o.y1 - o.y0);
+}
+
+// Entries offsets[i] .. offsets[i + 1) belong to Gaussian i: the scan was taken over the very counts this loop runs, so
+// nothing is written at or beyond offsets[n] (= the entry count the buffers were sized for).
+__global__ __launch_bounds__(TPB) void k_raster_duplicate(int n, int gx, const int4 *__restrict__ rect,
+                                                          const float4 *__restrict__ rec0,
+                                                          const uint64_t *__restrict__ offsets, uint64_t *keys, uint32_t *vals) {
+  int i = blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  int4 r = rect[i];
+  if (r.z <= r.x || r.w <= r.y) return;
+  uint64_t at = offsets[i];
+  const uint64_t depth = __float_as_uint(rec0[i].w);  // positive: the bits order like the value
+  for (int y = r.y; y < r.w; ++y)
+    for (int x = r.x; x < r.z; ++x) {
+      keys[at] = ((uint64_t)(uint32_t)(y * gx + x) << 32) | depth;
+      vals[at] = (uint32_t)i;
+      ++at;
+    }
+}
+
+// ranges[] is zeroed before: a tile without entries keeps (0, 0)
+__global__ __launch_bounds__(TPB) void k_raster_ranges(int64_t total, const uint64_t *__restrict__ keys, uint2 *ranges) {
+  int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (e >= total) return;
+  uint32_t tile = (uint32_t)(keys[e] >> 32);
+  if (e == 0) {
+    ranges[tile].x = 0;
+  } else {
+    uint32_t prev = (uint32_t)(keys[e - 1] >> 32);
+    if (prev != tile) { ranges[prev].y = (uint32_t)e; ranges[tile].x = (uint32_t)e; }
+  }
+  if (e == total - 1) ranges[tile].y = (uint32_t)total;
+}
+
+// One workgroup per tile, lane t = pixel (t % 16, t / 16) of it: wave w owns pixel rows 4 w .. 4 w + 3.  The tile's list is
+// consumed in batches of TPB entries: lane t fetches the record of entry base + t into LDS (two float4 and the colour,
+// 11 KB per workgroup), then every lane walks the batch out of LDS -- the address is the same for all lanes, so the reads
+// are broadcasts without bank conflicts.  The count barrier at the top of a batch is also what keeps a fast lane from
+// overwriting records a slow lane still reads.  Lanes outside the image take part in staging and barriers, count as
+// done from the start and write nothing.
+__global__ __launch_bounds__(TPB) void k_raster_render(int W, int H, int gx, const uint2 *__restrict__ ranges,
+                                                       const uint32_t *__restrict__ vals, const float4 *__restrict__ rec0,
+                                                       const float4 *__restrict__ rec1, const float *__restrict__ colour,
+                                                       float bg_r, float bg_g, float bg_b, float *out_color, float *out_alpha) {
+  __shared__ float4 s0[TPB], s1[TPB];
+  __shared__ float sr[TPB], sg[TPB], sb[TPB];
+  const int t = threadIdx.x;
+  const int x = blockIdx.x * TILE + (t % TILE), y = blockIdx.y * TILE + (t / TILE);
+  const bool inside = x < W && y < H;
+  const uint2 range = ranges[blockIdx.y * gx + blockIdx.x];
+  const float fx = (float)x, fy = (float)y;
+  rast::Pixel p{1.f, 0.f, 0.f, 0.f};
+  bool done = !inside;
+  for (uint32_t base = range.x; base < range.y; base += TPB) {
+    if (__syncthreads_count(done) == TPB) break;
+    const uint32_t e = base + t;
+    if (e < range.y) {
+      const size_t g = vals[e];
+      s0[t] = rec0[g]; s1[t] = rec1[g];
+      sr[t] = colour[3 * g]; sg[t] = colour[3 * g + 1]; sb[t] = colour[3 * g + 2];
+    }
+    __syncthreads();
+    const int nb = (int)min((uint32_t)TPB, range.y - base);
+    for (int j = 0; !done && j < nb; ++j) {
+      const float4 a = s0[j], c = s1[j];
+      done = rast::blend(p, a.x - fx, a.y - fy, c.x, c.y, c.z, a.z, rast::V3{sr[j], sg[j], sb[j]});
+    }
+  }
+  if (inside) {
+    const size_t at = (size_t)y * W + x, plane = (size_t)W * H;
+    out_color[at] = p.r + p.T * bg_r;
+    out_color[plane + at] = p.g + p.T * bg_g;
+    out_color[2 * plane + at] = p.b + p.T * bg_b;
+    out_alpha[at] = 1.f - p.T;
+  }
+}
+
+// touched[i] > 0 exactly when radii[i] > 0 (k_raster_preprocess), and unlike radii it is the handle's own memory
+__global__ __launch_bounds__(TPB) void k_raster_counts(int tiles, const uint2 *ranges, int n, const uint32_t *touched, int32_t *counts) {
+  int i = blockIdx.x * TPB + threadIdx.x;
+  if (i < tiles) atomicMax(&counts[0], (int32_t)(ranges[i].y - ranges[i].x));
+  if (i < n && touched[i] > 0) atomicAdd(&counts[1], 1);
+}
+
+int check(hipError_t e) { return e == hipSuccess ? MPMHIP_OK : MPMHIP_ERR_HIP; }
+#define RS_CHECK(expr) do { if (int rc_ = check(expr)) return rc_; } while (0)
+
+unsigned blocks(int64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
+
+template <class T>
+int regrow(T *&p, size_t count) {
+  if (p) RS_CHECK(hipFree(p));
+  p = nullptr;
+  return check(hipMalloc((void **)&p, count * sizeof(T)));
+}
+
+// capacity that holds `need`: at least twice the old one, so that a slowly growing scene reallocates O(log) times
+template <class I>
+I grown(I cap, I need) { return need > 2 * cap ? need : 2 * cap; }
+
+// temporary storage of a rocPRIM call: asked for with the call's own arguments every frame (a host-side computation)
+int reserve_tmp(mpmhip_raster *r, void *&p, size_t &have, size_t need) {
+  if (need <= have) return MPMHIP_OK;
+  RS_CHECK(hipStreamSynchronize(r->stream));
+  const size_t cap = grown(have, need);
+  char *tmp = (char *)p;
+  p = nullptr;
+  have = 0;
+  if (int rc = regrow(tmp, cap)) return rc;
+  p = tmp;
+  have = cap;
+  return MPMHIP_OK;
+}
+
+int reserve_gaussians(mpmhip_raster *r, int n) {
+  if (n <= r->cap_n) return MPMHIP_OK;
+  RS_CHECK(hipStreamSynchronize(r->stream));  // nothing in flight may still read what is freed
+  const int cap = grown(r->cap_n, n);
+  r->cap_n = 0;
+  if (int rc = regrow(r->rec0, (size_t)cap)) return rc;
+  if (int rc = regrow(r->rec1, (size_t)cap)) return rc;
+  if (int rc = regrow(r->colour, (size_t)cap * 3)) return rc;
+  if (int rc = regrow(r->rect, (size_t)cap)) return rc;
+  if (int rc = regrow(r->touched, (size_t)cap + 1)) return rc;
+  if (int rc = regrow(r->offsets, (size_t)cap + 1)) return rc;
+  r->cap_n = cap;
+  return MPMHIP_OK;
+}
+
+int reserve_entries(mpmhip_raster *r, size_t total) {
+  if (total <= r->cap_e) return MPMHIP_OK;
+  RS_CHECK(hipStreamSynchronize(r->stream));
+  const size_t cap = grown(r->cap_e, total);
+  r->cap_e = 0;
+  for (int k = 0; k < 2; ++k) {
+    if (int rc = regrow(r->keys[k], cap)) return rc;
+    if (int rc = regrow(r->vals[k], cap)) return rc;
+  }
+  r->cap_e = cap;
+  return MPMHIP_OK;
+}
+
+int reserve_tiles(mpmhip_raster *r, int tiles) {
+  if (tiles <= r->cap_tiles) return MPMHIP_OK;
+  RS_CHECK(hipStreamSynchronize(r->stream));
+  const int cap = grown(r->cap_tiles, tiles);
+  r->cap_tiles = 0;
+  if (int rc = regrow(r->ranges, (size_t)cap)) return rc;
+  r->cap_tiles = cap;
+  return MPMHIP_OK;
+}
+
+// stage k of the frame ends here (profiling only)
+int mark(mpmhip_raster *r, int k) { return r->profile ? check(hipEventRecord(r->ev[k], r->stream)) : MPMHIP_OK; }
+
+unsigned bits_for(int tiles) {  // ceil(log2(tiles))
+  unsigned b = 0;
+  while (((int64_t)1 << b) < tiles) ++b;
+  return b;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mpmhip_raster_create(int32_t device, void *stream, mpmhip_raster **out) {
+  if (!out) return MPMHIP_ERR_INVALID;
+  *out = nullptr;
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0 || device < 0 || device >= n_dev) return MPMHIP_ERR_NO_DEVICE;
+  RS_CHECK(hipSetDevice(device));
+  mpmhip_raster *r = new (std::nothrow) mpmhip_raster();
+  if (!r) return MPMHIP_ERR_HIP;
+  r->device = device;
+  r->stream = (hipStream_t)stream;
+  if (hipHostMalloc((void **)&r->h_total, sizeof(uint64_t), hipHostMallocDefault) != hipSuccess ||
+      hipMalloc((void **)&r->d_counts, 2 * sizeof(int32_t)) != hipSuccess) {
+    mpmhip_raster_destroy(r);
+    return MPMHIP_ERR_HIP;
+  }
+  *out = r;
+  return MPMHIP_OK;
+}
+
+void mpmhip_raster_destroy(mpmhip_raster *r) {
+  if (!r) return;
+  (void)hipSetDevice(r->device);
+  (void)hipStreamSynchronize(r->stream);
+  void *dev[] = {r->rec0, r->rec1, r->colour, r->rect, r->touched, r->offsets, r->scan_tmp, r->keys[0], r->keys[1],
+                 r->vals[0], r->vals[1], r->sort_tmp, r->ranges, r->d_counts};
+  for (void *p : dev)
+    if (p) (void)hipFree(p);
+  if (r->h_total) (void)hipHostFree(r->h_total);
+  for (hipEvent_t e : r->ev)
+    if (e) (void)hipEventDestroy(e);
+  delete r;
+}
+
+int mpmhip_raster_forward(mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, const float *means3D, const float *shs,
+                          int32_t n_sh_coeffs, const float *colors_precomp, const float *opacities, const float *scales,
+                          const float *rotations, const float *cov3D_precomp, float *out_color, float *out_alpha,
+                          int32_t *radii) {
+  if (!r || !s || n < 0 || s->image_height <= 0 || s->image_width <= 0 || !out_color || !out_alpha) return MPMHIP_ERR_INVALID;
+  if (!s->viewmatrix || !s->projmatrix || !s->campos) return MPMHIP_ERR_INVALID;
+  if (n > 0) {
+    if (!means3D || !opacities || !radii) return MPMHIP_ERR_INVALID;
+    if ((shs != nullptr) == (colors_precomp != nullptr)) return MPMHIP_ERR_INVALID;
+    const bool sr = scales && rotations;
+    if ((scales != nullptr) != (rotations != nullptr) || sr == (cov3D_precomp != nullptr)) return MPMHIP_ERR_INVALID;
+    if (shs && (s->sh_degree < 0 || s->sh_degree > 3 || n_sh_coeffs < (s->sh_degree + 1) * (s->sh_degree + 1))) return MPMHIP_ERR_INVALID;
+  }
+  const int W = s->image_width, H = s->image_height;
+  const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
+  if ((int64_t)gx * gy > INT32_MAX || gy > 65535) return MPMHIP_ERR_LIMIT;
+  const int tiles = gx * gy;
+  RS_CHECK(hipSetDevice(r->device));
+  hipStream_t st = r->stream;
+  if (int rc = reserve_tiles(r, tiles)) return rc;
+  if (int rc = reserve_gaussians(r, n > 0 ? n : 1)) return rc;
+  RS_CHECK(hipMemsetAsync(r->ranges, 0, (size_t)tiles * sizeof(uint2), st));
+  r->last_n = n; r->last_tiles = tiles; r->last_entries = 0;
+
+  uint64_t total = 0;
+  if (int rc = mark(r, 0)) return rc;
+  if (n > 0) {
+    Camera cam{W, H, gx, gy, s->tanfovx, s->tanfovy, s->scale_modifier, s->sh_degree, s->viewmatrix, s->projmatrix, s->campos};
+    hipLaunchKernelGGL(k_raster_preprocess, blocks((int64_t)n + 1), TPB, 0, st, n, cam, means3D, shs, n_sh_coeffs, colors_precomp,
+                       opacities, scales, rotations, cov3D_precomp, r->rec0, r->rec1, r->colour, r->rect, r->touched, radii);
+    RS_CHECK(hipGetLastError());
+    if (int rc = mark(r, 1)) return rc;
+    size_t tmp = 0;
+    RS_CHECK(rocprim::exclusive_scan(nullptr, tmp, r->touched, r->offsets, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
+    if (int rc = reserve_tmp(r, r->scan_tmp, r->scan_tmp_bytes, tmp)) return rc;
+    RS_CHECK(rocprim::exclusive_scan(r->scan_tmp, tmp, r->touched, r->offsets, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
+    RS_CHECK(hipMemcpyAsync(r->h_total, r->offsets + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    RS_CHECK(hipStreamSynchronize(st));  // the one synchronisation of a frame
+    total = *r->h_total;
+    if (total > (uint64_t)INT32_MAX) return MPMHIP_ERR_LIMIT;
+  } else if (int rc = mark(r, 1)) {
+    return rc;
+  }
+  if (int rc = mark(r, 2)) return rc;
+  if (total > 0) {
+    if (int rc = reserve_entries(r, (size_t)total)) return rc;
+    hipLaunchKernelGGL(k_raster_duplicate, blocks(n), TPB, 0, st, n, gx, (const int4 *)r->rect, (const float4 *)r->rec0,
+                       (const uint64_t *)r->offsets, r->keys[0], r->vals[0]);
+    RS_CHECK(hipGetLastError());
+    if (int rc = mark(r, 3)) return rc;
+    const unsigned end_bit = 32u + bits_for(tiles);
+    size_t tmp = 0;
+    RS_CHECK(rocprim::radix_sort_pairs(nullptr, tmp, r->keys[0], r->keys[1], r->vals[0], r->vals[1], (size_t)total, 0u, end_bit, st));
+    if (int rc = reserve_tmp(r, r->sort_tmp, r->sort_tmp_bytes, tmp)) return rc;
+    RS_CHECK(rocprim::radix_sort_pairs(r->sort_tmp, tmp, r->keys[0], r->keys[1], r->vals[0], r->vals[1], (size_t)total, 0u,
+                                       end_bit, st));
+    if (int rc = mark(r, 4)) return rc;
+    hipLaunchKernelGGL(k_raster_ranges, blocks((int64_t)total), TPB, 0, st, (int64_t)total, (const uint64_t *)r->keys[1], r->ranges);
+    RS_CHECK(hipGetLastError());
+  } else {
+    if (int rc = mark(r, 3)) return rc;
+    if (int rc = mark(r, 4)) return rc;
+  }
+  if (int rc = mark(r, 5)) return rc;
+  r->last_entries = (int64_t)total;
+  hipLaunchKernelGGL(k_raster_render, dim3((unsigned)gx, (unsigned)gy), TPB, 0, st, W, H, gx, (const uint2 *)r->ranges,
+                     (const uint32_t *)r->vals[1], (const float4 *)r->rec0, (const float4 *)r->rec1, (const float *)r->colour,
+                     s->bg[0], s->bg[1], s->bg[2], out_color, out_alpha);
+  RS_CHECK(hipGetLastError());
+  if (r->profile) {
+    if (int rc = mark(r, 6)) return rc;
+    RS_CHECK(hipEventSynchronize(r->ev[6]));
+    for (int k = 0; k < MPMHIP_RASTER_STAGES; ++k) {
+      float ms = 0.f;
+      RS_CHECK(hipEventElapsedTime(&ms, r->ev[k], r->ev[k + 1]));
+      r->stage_ms[k] += ms;
+    }
+    ++r->profiled_frames;
+  }
+  return MPMHIP_OK;
+}
+
+int mpmhip_raster_profile(mpmhip_raster *r, int32_t on, double *stage_ms, int64_t *frames) {
+  if (!r) return MPMHIP_ERR_INVALID;
+  RS_CHECK(hipSetDevice(r->device));
+  if (stage_ms) for (int k = 0; k < MPMHIP_RASTER_STAGES; ++k) stage_ms[k] = r->stage_ms[k];
+  if (frames) *frames = r->profiled_frames;
+  if (on && !r->profile) {
+    for (auto &e : r->ev)
+      if (!e) RS_CHECK(hipEventCreate(&e));
+    for (double &v : r->stage_ms) v = 0.0;
+    r->profiled_frames = 0;
+  }
+  r->profile = on != 0;
+  return MPMHIP_OK;
+}
+
+int mpmhip_raster_stats(const mpmhip_raster *r, mpmhip_raster_stats_t *out) {
+  if (!r || !out) return MPMHIP_ERR_INVALID;
+  RS_CHECK(hipSetDevice(r->device));
+  int32_t counts[2] = {0, 0};
+  if (r->last_tiles > 0) {
+    RS_CHECK(hipMemsetAsync(r->d_counts, 0, sizeof(counts), r->stream));
+    const int m = r->last_tiles > r->last_n ? r->last_tiles : r->last_n;
+    hipLaunchKernelGGL(k_raster_counts, blocks(m), TPB, 0, r->stream, r->last_tiles, (const uint2 *)r->ranges, r->last_n,
+                       (const uint32_t *)r->touched, r->d_counts);
+    RS_CHECK(hipGetLastError());
+    RS_CHECK(hipMemcpyAsync(counts, r->d_counts, sizeof(counts), hipMemcpyDeviceToHost, r->stream));
+    RS_CHECK(hipStreamSynchronize(r->stream));
+  }
+  out->n_entries = r->last_entries;
+  out->max_tile_entries = counts[0];
+  out->n_visible = counts[1];
+  out->scratch_bytes = (int64_t)((size_t)r->cap_n * (2 * sizeof(float4) + 3 * sizeof(float) + sizeof(int4)) +
+                                 ((size_t)r->cap_n + 1) * (sizeof(uint32_t) + sizeof(uint64_t)) + r->scan_tmp_bytes +
+                                 r->cap_e * 2 * (sizeof(uint64_t) + sizeof(uint32_t)) + r->sort_tmp_bytes +
+                                 (size_t)r->cap_tiles * sizeof(uint2));
+  return MPMHIP_OK;
+}
+
+}  // extern "C"

@@ -120,3 +120,22 @@ def write_geo_metric_npz(directory, chamfer, fscore):
     path = os.path.join(directory, "geo_metric.npz")
     np.savez(path, **{"CD": np.asarray(chamfer, np.float64), "F-Score": np.asarray(fscore, np.float64)})
     return path
+
+
+def write_png(path, image):
+    """An RGB image [3, H, W] with values in [0, 1] (what the rasteriser returns; torchvision.utils.save_image's rounding,
+    train_material_params.py:872) as an 8-bit PNG, with nothing but zlib."""
+    import struct
+    import zlib
+    a = np.asarray(image, np.float32)
+    if a.ndim != 3 or a.shape[0] != 3:
+        raise ValueError("write_png expects an array of shape [3, H, W]")
+    px = (np.clip(a, 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8).transpose(1, 2, 0)
+    h, w = px.shape[:2]
+    raw = b"".join(b"\x00" + px[y].tobytes() for y in range(h))
+    chunk = lambda tag, data: struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) +
+                chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
+    return path

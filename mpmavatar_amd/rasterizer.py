@@ -1,0 +1,209 @@
+"""Forward Gaussian rasteriser on the GPU behind the names of the reference's ``diff_gauss`` extension
+(/root/reference/gaussian_renderer/__init__.py:14,36-103): the last step of the chain solver -> ``MeshFrames`` ->
+``BoundGaussians.render_inputs`` -> image,
+
+    settings = GaussianRasterizationSettings(image_height=h, image_width=w, tanfovx=..., tanfovy=..., bg=bg_color,
+                                             scale_modifier=1.0, viewmatrix=cam.world_view_transform,
+                                             projmatrix=cam.full_proj_transform, sh_degree=pc.active_sh_degree,
+                                             campos=cam.camera_center, prefiltered=False, debug=False)
+    image, _, _, mask, radii, _ = GaussianRasterizer(raster_settings=settings)(**gaussians.render_inputs(frames, ...))
+
+over the HIP pipeline of ``csrc/raster.hip`` (``mpmhip_raster_forward``).  With ``mpmavatar_amd/compat`` on PYTHONPATH the
+reference's ``from diff_gauss import GaussianRasterizationSettings, GaussianRasterizer`` resolves to these two names.
+
+FORWARD ONLY.  There is no backward pass: ``requires_grad`` on inputs such as ``means2D`` is accepted and ignored, and the
+outputs carry no graph.  The eval loop (train_material_params.py:857-872) and the demo (run_demo.py:540-604) need no more;
+``train_appearance.py``, which optimises the Gaussians through the renderer, cannot use it.
+
+Each call blocks the host once (the pipeline reads one count back to size its sort, csrc/raster.hip).  The three floats of
+``bg`` are read from the device the first time a given tensor is seen and kept until it is modified in place or freed, so
+a loop that renders against one background tensor, as the reference's does, adds no second wait.  No CPU fallback: tensors
+must live on an MI355X.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import weakref
+from typing import NamedTuple
+
+import torch
+
+from . import _lib as L
+
+
+class GaussianRasterizationSettings(NamedTuple):  # fields and order of gaussian_renderer/__init__.py:36-49
+    image_height: int
+    image_width: int
+    tanfovx: float
+    tanfovy: float
+    bg: torch.Tensor
+    scale_modifier: float
+    viewmatrix: torch.Tensor
+    projmatrix: torch.Tensor
+    sh_degree: int
+    campos: torch.Tensor
+    prefiltered: bool
+    debug: bool
+
+
+def _chk(t, dtype, name, shape=None):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+        raise RuntimeError(f"{name}: expected a contiguous {dtype} tensor on the GPU")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+class _Handle:
+    """One mpmhip_raster per (device, stream): the scratch is reused from frame to frame.  The handle keeps the
+    torch.cuda.Stream object it was made for: torch's own streams come from a pool that is never destroyed, and for an
+    ExternalStream the wrapper does not own the hipStream_t -- whoever destroys such a stream must not render on a new one
+    at the same address (``GaussianRasterizer(..., private_scratch=True)`` is the way out)."""
+
+    def __init__(self, device_index, stream):
+        self.lib = L.load()
+        self.ptr = L.vp()
+        self.stream = stream
+        self.last_user = None     # weak reference to the rasteriser whose frame the handle's counts describe
+        rc = self.lib.mpmhip_raster_create(device_index, stream.cuda_stream, C.byref(self.ptr))
+        if rc != L.OK:
+            raise L.MPMHipError(rc, "mpmhip_raster_create failed")
+        weakref.finalize(self, self.lib.mpmhip_raster_destroy, self.ptr)
+
+
+_SHARED = {}
+_BG = {}    # id(bg tensor) -> (weak reference, version counter, three floats)
+
+
+def _bg_floats(bg):
+    """The background colour as three host floats; one device-to-host copy per tensor and version, not per frame."""
+    hit = _BG.get(id(bg))
+    if hit is not None and hit[0]() is bg and hit[1] == bg._version:
+        return hit[2]
+    vals = tuple(float(v) for v in bg.detach().reshape(3).tolist())
+    key = id(bg)
+    _BG[key] = (weakref.ref(bg, lambda _, key=key: _BG.pop(key, None)), bg._version, vals)
+    return vals
+
+
+def look_at_camera(eye, target, fov_deg, device, znear=0.01, zfar=100.0):
+    """(world_view_transform, full_proj_transform, camera_center, tan(fov / 2)) of a square-pixel camera at `eye` looking
+    at `target`, world +y up, in the reference's layout (scene/cameras.py:26-39: transposed, row vectors from the left;
+    +z forward, +y down in the image).  For the example and the benchmark, which have no dataset camera."""
+    import numpy as np
+    eye, target = np.asarray(eye, np.float64), np.asarray(target, np.float64)
+    fwd = (target - eye) / np.linalg.norm(target - eye)
+    right = np.cross(fwd, [0.0, 1.0, 0.0])
+    right /= np.linalg.norm(right)
+    down = np.cross(fwd, right)
+    R = np.stack([right, down, fwd])                    # world -> camera
+    w2c = np.eye(4)
+    w2c[:3, :3], w2c[:3, 3] = R, -R @ eye
+    t = math.tan(math.radians(fov_deg) / 2)
+    P = np.zeros((4, 4))
+    P[0, 0] = P[1, 1] = 1.0 / t
+    P[2, 2], P[2, 3], P[3, 2] = zfar / (zfar - znear), -(zfar * znear) / (zfar - znear), 1.0
+    f32 = lambda a: torch.tensor(np.asarray(a, np.float32), device=device)
+    return f32(w2c.T), f32(w2c.T @ P.T), f32(eye), t
+
+
+class GaussianRasterizer:
+    """``GaussianRasterizer(raster_settings)(means3D=, means2D=, shs=, colors_precomp=, opacities=, scales=, rotations=,
+    cov3Ds_precomp=)`` -> ``(image [3, H, W], None, None, alpha [1, H, W], radii [N] int32, None)``: the 6-tuple of the
+    reference's call, of which it reads slots 0, 3 and 4 (gaussian_renderer/__init__.py:95).  Forward only (module docstring)."""
+
+    def __init__(self, raster_settings: GaussianRasterizationSettings, private_scratch: bool = False):
+        """The reference builds a new rasteriser for every frame (gaussian_renderer/__init__.py:51), so the scratch is shared
+        by all instances (one handle per device and stream).  private_scratch=True gives this instance handles of its own."""
+        self.raster_settings = raster_settings
+        self._handles = {} if private_scratch else _SHARED
+        self._last = None
+
+    def _handle(self, dev):
+        index = dev.index if dev.index is not None else torch.cuda.current_device()
+        stream = torch.cuda.current_stream(index)
+        key = (index, stream.cuda_stream)
+        if key not in self._handles:
+            self._handles[key] = _Handle(index, stream)
+        return self._handles[key]
+
+    def stats(self):
+        """{"n_entries", "max_tile_entries", "n_visible", "scratch_bytes"} of this instance's newest call (synchronises).
+        The counts live in the handle, which other instances share: asking after another instance has rendered on the same
+        device and stream raises instead of reporting that one's frame."""
+        if self._last is None:
+            raise RuntimeError("nothing has been rendered yet")
+        if self._last.last_user is None or self._last.last_user() is not self:
+            raise RuntimeError("another rasteriser has rendered on this device and stream since: its counts replaced these")
+        st = L.RasterStats()
+        rc = self._last.lib.mpmhip_raster_stats(self._last.ptr, C.byref(st))
+        if rc != L.OK:
+            raise L.MPMHipError(rc, "mpmhip_raster_stats failed")
+        return {k: int(getattr(st, k)) for k, _ in L.RasterStats._fields_}
+
+    def forward(self, means3D, means2D=None, opacities=None, shs=None, colors_precomp=None, scales=None, rotations=None,
+                cov3Ds_precomp=None):
+        s = self.raster_settings
+        if (shs is None) == (colors_precomp is None):
+            raise RuntimeError("Please provide exactly one of either SHs or precomputed colors!")
+        if (scales is None) != (rotations is None) or (scales is None) == (cov3Ds_precomp is None):
+            raise RuntimeError("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+        if opacities is None:
+            raise RuntimeError("opacities: expected a tensor")
+        h, w = int(s.image_height), int(s.image_width)
+        if h <= 0 or w <= 0:
+            raise RuntimeError("image_height and image_width must be positive")
+        for name, t in (("means3D", means3D), ("opacities", opacities), ("shs", shs), ("colors_precomp", colors_precomp),
+                        ("scales", scales), ("rotations", rotations), ("cov3Ds_precomp", cov3Ds_precomp)):
+            if t is not None and not isinstance(t, torch.Tensor):
+                raise RuntimeError(f"{name}: expected a tensor")
+        with torch.no_grad():
+            m = _chk(means3D.detach(), torch.float32, "means3D")
+            if m.dim() != 2 or m.shape[1] != 3:
+                raise RuntimeError(f"means3D: expected shape (n, 3), got {tuple(m.shape)}")
+            n, dev = m.shape[0], m.device
+            same = lambda t, name, shape: _chk(t.detach() if isinstance(t, torch.Tensor) else t, torch.float32, name, shape)
+            op = same(opacities, "opacities", (n, 1)) if opacities.dim() == 2 else same(opacities, "opacities", (n,))
+            n_sh, deg = 0, int(s.sh_degree)
+            if shs is not None:
+                if not 0 <= deg <= 3:
+                    raise RuntimeError("sh_degree must be 0, 1, 2 or 3")
+                if shs.dim() != 3 or shs.shape[1] < (deg + 1) ** 2:
+                    raise RuntimeError(f"shs: expected shape (n, >= {(deg + 1) ** 2}, 3) for sh_degree {deg}")
+                n_sh = shs.shape[1]
+                shs = same(shs, "shs", (n, n_sh, 3))
+            else:
+                colors_precomp = same(colors_precomp, "colors_precomp", (n, 3))
+            if scales is not None:
+                scales, rotations = same(scales, "scales", (n, 3)), same(rotations, "rotations", (n, 4))
+            else:
+                cov3Ds_precomp = same(cov3Ds_precomp, "cov3Ds_precomp", (n, 6))
+            # the reference's world_view_transform is a transposed view (scene/cameras.py:26): the three small camera
+            # tensors are made contiguous here instead of being refused
+            small = lambda t, name, shape: same(t.contiguous() if isinstance(t, torch.Tensor) else t, name, shape)
+            view, proj = small(s.viewmatrix, "viewmatrix", (4, 4)), small(s.projmatrix, "projmatrix", (4, 4))
+            campos, bg = small(s.campos, "campos", (3,)), s.bg
+            if not (isinstance(bg, torch.Tensor) and bg.numel() == 3):
+                raise RuntimeError("bg: expected a tensor of 3 values")
+            for name, t in (("opacities", op), ("shs", shs), ("colors_precomp", colors_precomp), ("scales", scales),
+                            ("rotations", rotations), ("cov3Ds_precomp", cov3Ds_precomp), ("viewmatrix", view),
+                            ("projmatrix", proj), ("campos", campos)):
+                if t is not None and t.device != dev:
+                    raise RuntimeError(f"{name}: expected a tensor on {dev}")
+            bg3 = _bg_floats(bg)
+            cs = L.RasterSettings(h, w, float(s.tanfovx), float(s.tanfovy), L.f3(*bg3), float(s.scale_modifier), deg,
+                                  view.data_ptr(), proj.data_ptr(), campos.data_ptr())
+            image = torch.empty(3, h, w, dtype=torch.float32, device=dev)
+            alpha = torch.empty(1, h, w, dtype=torch.float32, device=dev)
+            radii = torch.empty(n, dtype=torch.int32, device=dev)
+            hd = self._handle(dev)
+            p = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+            rc = hd.lib.mpmhip_raster_forward(hd.ptr, C.byref(cs), n, p(m), p(shs), n_sh, p(colors_precomp), p(op), p(scales),
+                                              p(rotations), p(cov3Ds_precomp), image.data_ptr(), alpha.data_ptr(), p(radii))
+            if rc != L.OK:
+                raise L.MPMHipError(rc, "mpmhip_raster_forward failed")
+            self._last, hd.last_user = hd, weakref.ref(self)
+        return image, None, None, alpha, radii, None
+
+    __call__ = forward

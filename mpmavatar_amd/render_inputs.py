@@ -5,8 +5,8 @@ The reference writes every simulated frame to an OBJ file, has Blender bake ambi
 poses the Gaussians and renders (train_material_params.py:819-845, run_demo.py:540-604).  The geometry half of that detour is not
 needed: ``MeshFrames.set_mesh_by_verts`` takes the solver's ``particle_x`` as it lies in HBM, and ``BoundGaussians.render_inputs``
 returns exactly ``means3D, means2D, opacities, scales, rotations`` (+ the caller's ``shs`` / ``colors_precomp`` and the ``extra``
-primitives concatenated behind, :84-91) in one launch (``mpmhip_render_inputs``).  The rasteriser (diff_gauss) and the AO bake stay
-out of scope; the OBJ files are still what Blender needs (``io_formats.write_uv_obj``), but nothing has to be read back from them.
+primitives concatenated behind, :84-91) in one launch (``mpmhip_render_inputs``).  The rasteriser they go to is
+``mpmavatar_amd/rasterizer.py``; the AO bake stays out of scope, and the OBJ files are still what Blender needs (``io_formats.write_uv_obj``), but nothing has to be read back from them.
 
     frames = MeshFrames(faces);  frames.set_mesh_by_verts(sim2wld(state.particle_x[n_e + n_t:]))
     args = gaussians.render_inputs(frames, override_color=colors, extra=(xyz, colors, opacity, scales, rotations))
