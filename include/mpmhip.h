@@ -359,10 +359,10 @@ int mpmhip_nn_dist2(int32_t device, void *stream, const float *src, int32_t n_sr
 int mpmhip_geo_reduce(int32_t device, void *stream, const float *dist2_12, int32_t n1, const float *dist2_21, int32_t n2,
                       double tau, double *scratch, double *out);
 
-/* ---- after the solver: the forward Gaussian rasteriser --------------------------------------------------------------
+/* ---- after the solver: the Gaussian rasteriser ----------------------------------------------------------------------
  * What the reference calls as diff_gauss.GaussianRasterizer (gaussian_renderer/__init__.py:14,36-103; the extension is not
- * vendored there, README.md:51): the published 3D Gaussian splatting forward pass, forward only, as the eval loop
- * (train_material_params.py:857-872) and the demo (run_demo.py:540-604) use it.  All arithmetic fp32, no floating-point
+ * vendored there, README.md:51): the published 3D Gaussian splatting forward pass, as the eval loop
+ * (train_material_params.py:857-872) and the demo (run_demo.py:540-604) use it; the backward pass follows below.  All arithmetic fp32, no floating-point
  * atomics: the same input gives the same bits.
  *
  * GaussianRasterizationSettings, gaussian_renderer/__init__.py:36-49 (prefiltered and debug have no meaning here).
@@ -407,6 +407,46 @@ int mpmhip_raster_forward(mpmhip_raster *r, const mpmhip_raster_settings *s, int
                           int32_t n_sh_coeffs, const float *colors_precomp, const float *opacities, const float *scales,
                           const float *rotations, const float *cov3D_precomp, float *out_color, float *out_alpha,
                           int32_t *radii);
+/* ---- the rasteriser's backward pass: what train_appearance.py:123-155 needs ---------------------------------------------
+ * There the render call (gaussian_renderer/__init__.py:95-103 with override_color, scales and rotations) is followed by
+ * image * mask, L1 + SSIM + LPIPS and loss.backward() (train_appearance.py:123-155), and viewspace_point_tensor.grad -- the
+ * gradient of means2D -- feeds the densification statistics (train_appearance.py:245-253).  The gradient is the exact
+ * derivative of the forward function above with every discrete decision held fixed (culling, radius, tile rectangle, depth
+ * order, power > 0, alpha < 1/255, the T < 1e-4 finish); the clamps -- alpha = min(0.99, .), the frustum clamp inside the
+ * Jacobian, max(0, sh + 0.5) -- have zero slope where they bind.  No floating-point atomics: the same input gives the same bits.
+ *
+ * A handle's scratch is overwritten by its next forward call, so a frame that will be differentiated is copied out:
+ *   mpmhip_raster_forward_grad  mpmhip_raster_forward (same arguments, same image / alpha / radii bits) that also records, per
+ *                               pixel, the final T and the position in its tile's list at which it stopped, and the map from a
+ *                               Gaussian's entries to their sorted positions
+ *   mpmhip_raster_saved_bytes   size of that frame's state and its number of (tile, Gaussian) entries; MPMHIP_ERR_STATE when the
+ *                               handle's newest frame was not a forward_grad
+ *   mpmhip_raster_save          asynchronous device-to-device copy of the state, on the handle's stream, into the caller's [dev]
+ *                               buffer of exactly that size (16-byte aligned): packed records and colours, sorted Gaussian
+ *                               indices, tile ranges, offsets, rectangles, the inverse map, per-pixel T and position
+ *   mpmhip_raster_backward      the settings and inputs of the forward call, the saved buffer with its two sizes, dL_dimage
+ *                               [3*H*W] and dL_dalpha [H*W] (either may be NULL = zeros), and the [dev] outputs: d_means3D [n*3]
+ *                               (projection + Jacobian of the 2D covariance + SH view direction), d_means2D [n*3] (dL/dpx * W/2,
+ *                               dL/dpy * H/2, 0: the gradient with respect to an additive NDC offset of the pixel centre),
+ *                               d_shs [n*n_sh_coeffs*3] OR d_colors_precomp [n*3], d_opacities [n], d_scales [n*3] and
+ *                               d_rotations [n*4] (through the normalisation of the quaternion) OR d_cov3D_precomp [n*6] (an
+ *                               off-diagonal value gets the sum of both positions it fills).  Every element is written, zeros
+ *                               for a culled Gaussian.  Any handle of the same device may run it (its own temporaries, 36 B per
+ *                               entry, live in the handle); asynchronous on that handle's stream.
+ * MPMHIP_ERR_INVALID and nothing launched: the conditions of mpmhip_raster_forward, a NULL saved buffer or required output, or
+ * saved_bytes that is not the size of a frame of this n, image size and n_entries. */
+int mpmhip_raster_forward_grad(mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, const float *means3D, const float *shs,
+                               int32_t n_sh_coeffs, const float *colors_precomp, const float *opacities, const float *scales,
+                               const float *rotations, const float *cov3D_precomp, float *out_color, float *out_alpha,
+                               int32_t *radii);
+int mpmhip_raster_saved_bytes(const mpmhip_raster *r, int64_t *bytes, int64_t *n_entries);
+int mpmhip_raster_save(mpmhip_raster *r, void *dst, int64_t bytes);
+int mpmhip_raster_backward(mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, const float *means3D, const float *shs,
+                           int32_t n_sh_coeffs, const float *colors_precomp, const float *opacities, const float *scales,
+                           const float *rotations, const float *cov3D_precomp, const void *saved, int64_t saved_bytes,
+                           int64_t n_entries, const float *dL_dimage, const float *dL_dalpha, float *d_means3D, float *d_means2D,
+                           float *d_shs, float *d_colors_precomp, float *d_opacities, float *d_scales, float *d_rotations,
+                           float *d_cov3D_precomp);
 /* counts of the newest frame; synchronous, runs one small count kernel */
 int mpmhip_raster_stats(const mpmhip_raster *r, mpmhip_raster_stats_t *out);
 /* Measurement only (tools/raster_bench.py; the counterpart of mpmhip_profile_enable for this pipeline): while on, every

@@ -110,6 +110,10 @@ SIGNATURES = {
     "mpmhip_raster_create": (C.c_int, [C.c_int32, vp, C.POINTER(vp)]),
     "mpmhip_raster_destroy": (None, [vp]),
     "mpmhip_raster_forward": (C.c_int, [vp, C.POINTER(RasterSettings), C.c_int32, vp, vp, C.c_int32] + [vp] * 8),
+    "mpmhip_raster_forward_grad": (C.c_int, [vp, C.POINTER(RasterSettings), C.c_int32, vp, vp, C.c_int32] + [vp] * 8),
+    "mpmhip_raster_saved_bytes": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mpmhip_raster_save": (C.c_int, [vp, vp, C.c_int64]),
+    "mpmhip_raster_backward": (C.c_int, [vp, C.POINTER(RasterSettings), C.c_int32, vp, vp, C.c_int32] + [vp] * 6 + [C.c_int64, C.c_int64] + [vp] * 10),
     "mpmhip_raster_stats": (C.c_int, [vp, C.POINTER(RasterStats)]),
     "mpmhip_raster_profile": (C.c_int, [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "mpmhip_dist_enable": (C.c_int, [vp]),

@@ -1,7 +1,7 @@
 // raster.hip -- forward Gaussian rasteriser: what the reference calls as diff_gauss.GaussianRasterizer
-// (/root/reference/gaussian_renderer/__init__.py:14,36-103), forward only, as the eval loop
-// (train_material_params.py:857-872) and the demo (run_demo.py:540-604) use it.  The math is raster_math.hpp; this file is
-// the pipeline:
+// (/root/reference/gaussian_renderer/__init__.py:14,36-103), as the eval loop (train_material_params.py:857-872) and the
+// demo (run_demo.py:540-604) use it, and its training flavour (mpmhip_raster_forward_grad), which also records what the
+// backward pass (raster_backward.hip) needs.  The math is raster_math.hpp; this file is the pipeline:
 //
 //   k_raster_preprocess  one lane per Gaussian: projection, conic, radius, tile rectangle, colour -> packed records
 //   rocprim::exclusive_scan of tiles_touched (n + 1 values: the last offset is the entry count)
@@ -23,55 +23,11 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-#include "../../include/mpmhip.h"
-#include "raster_math.hpp"
-
-struct mpmhip_raster {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  // per Gaussian (capacity cap_n)
-  int cap_n = 0;
-  float4 *rec0 = nullptr, *rec1 = nullptr;  // (px, py, opacity, depth), (A, B, C, 0)
-  float *colour = nullptr;                  // [n*3]
-  int4 *rect = nullptr;                     // x0 y0 x1 y1
-  uint32_t *touched = nullptr;              // [n + 1], the last one 0
-  uint64_t *offsets = nullptr;              // [n + 1] exclusive scan; offsets[n] = number of entries
-  void *scan_tmp = nullptr;
-  size_t scan_tmp_bytes = 0;
-  // per (tile, Gaussian) entry (capacity cap_e)
-  size_t cap_e = 0;
-  uint64_t *keys[2] = {nullptr, nullptr};
-  uint32_t *vals[2] = {nullptr, nullptr};
-  void *sort_tmp = nullptr;
-  size_t sort_tmp_bytes = 0;
-  // per tile (capacity cap_tiles)
-  int cap_tiles = 0;
-  uint2 *ranges = nullptr;
-  // small
-  uint64_t *h_total = nullptr;  // pinned
-  int32_t *d_counts = nullptr;  // [2]: longest tile list, Gaussians with radius > 0 (mpmhip_raster_stats)
-  // the last frame, for mpmhip_raster_stats
-  int64_t last_entries = 0;
-  int last_n = 0, last_tiles = 0;
-  // mpmhip_raster_profile: events between the stages of a frame (off by default: no events, no extra synchronisation)
-  bool profile = false;
-  hipEvent_t ev[MPMHIP_RASTER_STAGES + 1] = {};
-  double stage_ms[MPMHIP_RASTER_STAGES] = {};
-  int64_t profiled_frames = 0;
-};
+#include "raster_state.hpp"
 
 namespace {
 
-constexpr int TPB = 256;
-constexpr int TILE = rast::TILE;
-static_assert(TILE * TILE == TPB, "one lane per pixel of a tile");
-
-struct Camera {  // the scalar half of mpmhip_raster_settings plus its three device pointers
-  int W, H, gx, gy;
-  float tanfovx, tanfovy, scale_modifier;
-  int sh_degree;
-  const float *view, *proj, *campos;
-};
+using namespace raster_host;
 
 __global__ __launch_bounds__(TPB) void k_raster_preprocess(int n, Camera cam, const float *__restrict__ means,
                                                            const float *__restrict__ shs, int n_sh,
@@ -150,10 +106,14 @@ __global__ __launch_bounds__(TPB) void k_raster_ranges(int64_t total, const uint
 // are broadcasts without bank conflicts.  The count barrier at the top of a batch is also what keeps a fast lane from
 // overwriting records a slow lane still reads.  Lanes outside the image take part in staging and barriers, count as
 // done from the start and write nothing.
+// SAVE = the training flavour (mpmhip_raster_forward_grad): every pixel also stores its final T and the position in the
+// sorted entries at which it stopped -- the entry that finished it, or the end of its tile's range -- for the backward pass.
+template <bool SAVE>
 __global__ __launch_bounds__(TPB) void k_raster_render(int W, int H, int gx, const uint2 *__restrict__ ranges,
                                                        const uint32_t *__restrict__ vals, const float4 *__restrict__ rec0,
                                                        const float4 *__restrict__ rec1, const float *__restrict__ colour,
-                                                       float bg_r, float bg_g, float bg_b, float *out_color, float *out_alpha) {
+                                                       float bg_r, float bg_g, float bg_b, float *out_color, float *out_alpha,
+                                                       float *pix_T, uint32_t *pix_stop) {
   __shared__ float4 s0[TPB], s1[TPB];
   __shared__ float sr[TPB], sg[TPB], sb[TPB];
   const int t = threadIdx.x;
@@ -163,6 +123,7 @@ __global__ __launch_bounds__(TPB) void k_raster_render(int W, int H, int gx, con
   const float fx = (float)x, fy = (float)y;
   rast::Pixel p{1.f, 0.f, 0.f, 0.f};
   bool done = !inside;
+  uint32_t stop = range.y;
   for (uint32_t base = range.x; base < range.y; base += TPB) {
     if (__syncthreads_count(done) == TPB) break;
     const uint32_t e = base + t;
@@ -176,6 +137,9 @@ __global__ __launch_bounds__(TPB) void k_raster_render(int W, int H, int gx, con
     for (int j = 0; !done && j < nb; ++j) {
       const float4 a = s0[j], c = s1[j];
       done = rast::blend(p, a.x - fx, a.y - fy, c.x, c.y, c.z, a.z, rast::V3{sr[j], sg[j], sb[j]});
+      if constexpr (SAVE) {
+        if (done) stop = base + (uint32_t)j;
+      }
     }
   }
   if (inside) {
@@ -184,7 +148,22 @@ __global__ __launch_bounds__(TPB) void k_raster_render(int W, int H, int gx, con
     out_color[plane + at] = p.g + p.T * bg_g;
     out_color[2 * plane + at] = p.b + p.T * bg_b;
     out_alpha[at] = 1.f - p.T;
+    if constexpr (SAVE) { pix_T[at] = p.T; pix_stop[at] = stop; }
   }
+}
+
+// After the sort: where each entry went.  Before the sort Gaussian g's entries lie at offsets[g] + (ty - y0) (x1 - x0) +
+// (tx - x0) (k_raster_duplicate); inv[that] = the sorted position, so the backward pass finds a Gaussian's rows without a
+// search.  Every slot below `total` is written exactly once: the sort permutes the entries.
+__global__ __launch_bounds__(TPB) void k_raster_inverse(int64_t total, int gx, const uint64_t *__restrict__ keys,
+                                                        const uint32_t *__restrict__ vals, const int4 *__restrict__ rect,
+                                                        const uint64_t *__restrict__ offsets, uint32_t *inv) {
+  int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  if (e >= total) return;
+  const uint32_t g = vals[e], tile = (uint32_t)(keys[e] >> 32);
+  const int tx = (int)(tile % (uint32_t)gx), ty = (int)(tile / (uint32_t)gx);
+  const int4 r = rect[g];
+  inv[offsets[g] + (uint64_t)((ty - r.y) * (r.z - r.x) + (tx - r.x))] = (uint32_t)e;
 }
 
 // touched[i] > 0 exactly when radii[i] > 0 (k_raster_preprocess), and unlike radii it is the handle's own memory
@@ -192,74 +171,6 @@ __global__ __launch_bounds__(TPB) void k_raster_counts(int tiles, const uint2 *r
   int i = blockIdx.x * TPB + threadIdx.x;
   if (i < tiles) atomicMax(&counts[0], (int32_t)(ranges[i].y - ranges[i].x));
   if (i < n && touched[i] > 0) atomicAdd(&counts[1], 1);
-}
-
-int check(hipError_t e) { return e == hipSuccess ? MPMHIP_OK : MPMHIP_ERR_HIP; }
-#define RS_CHECK(expr) do { if (int rc_ = check(expr)) return rc_; } while (0)
-
-unsigned blocks(int64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
-
-template <class T>
-int regrow(T *&p, size_t count) {
-  if (p) RS_CHECK(hipFree(p));
-  p = nullptr;
-  return check(hipMalloc((void **)&p, count * sizeof(T)));
-}
-
-// capacity that holds `need`: at least twice the old one, so that a slowly growing scene reallocates O(log) times
-template <class I>
-I grown(I cap, I need) { return need > 2 * cap ? need : 2 * cap; }
-
-// temporary storage of a rocPRIM call: asked for with the call's own arguments every frame (a host-side computation)
-int reserve_tmp(mpmhip_raster *r, void *&p, size_t &have, size_t need) {
-  if (need <= have) return MPMHIP_OK;
-  RS_CHECK(hipStreamSynchronize(r->stream));
-  const size_t cap = grown(have, need);
-  char *tmp = (char *)p;
-  p = nullptr;
-  have = 0;
-  if (int rc = regrow(tmp, cap)) return rc;
-  p = tmp;
-  have = cap;
-  return MPMHIP_OK;
-}
-
-int reserve_gaussians(mpmhip_raster *r, int n) {
-  if (n <= r->cap_n) return MPMHIP_OK;
-  RS_CHECK(hipStreamSynchronize(r->stream));  // nothing in flight may still read what is freed
-  const int cap = grown(r->cap_n, n);
-  r->cap_n = 0;
-  if (int rc = regrow(r->rec0, (size_t)cap)) return rc;
-  if (int rc = regrow(r->rec1, (size_t)cap)) return rc;
-  if (int rc = regrow(r->colour, (size_t)cap * 3)) return rc;
-  if (int rc = regrow(r->rect, (size_t)cap)) return rc;
-  if (int rc = regrow(r->touched, (size_t)cap + 1)) return rc;
-  if (int rc = regrow(r->offsets, (size_t)cap + 1)) return rc;
-  r->cap_n = cap;
-  return MPMHIP_OK;
-}
-
-int reserve_entries(mpmhip_raster *r, size_t total) {
-  if (total <= r->cap_e) return MPMHIP_OK;
-  RS_CHECK(hipStreamSynchronize(r->stream));
-  const size_t cap = grown(r->cap_e, total);
-  r->cap_e = 0;
-  for (int k = 0; k < 2; ++k) {
-    if (int rc = regrow(r->keys[k], cap)) return rc;
-    if (int rc = regrow(r->vals[k], cap)) return rc;
-  }
-  r->cap_e = cap;
-  return MPMHIP_OK;
-}
-
-int reserve_tiles(mpmhip_raster *r, int tiles) {
-  if (tiles <= r->cap_tiles) return MPMHIP_OK;
-  RS_CHECK(hipStreamSynchronize(r->stream));
-  const int cap = grown(r->cap_tiles, tiles);
-  r->cap_tiles = 0;
-  if (int rc = regrow(r->ranges, (size_t)cap)) return rc;
-  r->cap_tiles = cap;
-  return MPMHIP_OK;
 }
 
 // stage k of the frame ends here (profiling only)
@@ -270,6 +181,30 @@ unsigned bits_for(int tiles) {  // ceil(log2(tiles))
   while (((int64_t)1 << b) < tiles) ++b;
   return b;
 }
+
+int reserve_grad(mpmhip_raster *r, size_t pixels, size_t total) {
+  if (pixels > r->cap_pix) {
+    RS_CHECK(hipStreamSynchronize(r->stream));
+    const size_t cap = grown(r->cap_pix, pixels);
+    r->cap_pix = 0;
+    if (int rc = regrow(r->pix_T, cap)) return rc;
+    if (int rc = regrow(r->pix_stop, cap)) return rc;
+    r->cap_pix = cap;
+  }
+  if (total > r->cap_inv) {
+    RS_CHECK(hipStreamSynchronize(r->stream));
+    const size_t cap = grown(r->cap_inv, total);
+    r->cap_inv = 0;
+    if (int rc = regrow(r->inv, cap)) return rc;
+    r->cap_inv = cap;
+  }
+  return MPMHIP_OK;
+}
+
+// grad = false is mpmhip_raster_forward: the render kernel's plain instantiation, no per-pixel state, nothing more allocated
+int forward_impl(mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, const float *means3D, const float *shs,
+                 int32_t n_sh_coeffs, const float *colors_precomp, const float *opacities, const float *scales,
+                 const float *rotations, const float *cov3D_precomp, float *out_color, float *out_alpha, int32_t *radii, bool grad);
 
 }  // namespace
 
@@ -299,7 +234,7 @@ void mpmhip_raster_destroy(mpmhip_raster *r) {
   (void)hipSetDevice(r->device);
   (void)hipStreamSynchronize(r->stream);
   void *dev[] = {r->rec0, r->rec1, r->colour, r->rect, r->touched, r->offsets, r->scan_tmp, r->keys[0], r->keys[1],
-                 r->vals[0], r->vals[1], r->sort_tmp, r->ranges, r->d_counts};
+                 r->vals[0], r->vals[1], r->sort_tmp, r->ranges, r->d_counts, r->pix_T, r->pix_stop, r->inv, r->rows};
   for (void *p : dev)
     if (p) (void)hipFree(p);
   if (r->h_total) (void)hipHostFree(r->h_total);
@@ -312,6 +247,58 @@ int mpmhip_raster_forward(mpmhip_raster *r, const mpmhip_raster_settings *s, int
                           int32_t n_sh_coeffs, const float *colors_precomp, const float *opacities, const float *scales,
                           const float *rotations, const float *cov3D_precomp, float *out_color, float *out_alpha,
                           int32_t *radii) {
+  return forward_impl(r, s, n, means3D, shs, n_sh_coeffs, colors_precomp, opacities, scales, rotations, cov3D_precomp, out_color,
+                      out_alpha, radii, false);
+}
+
+int mpmhip_raster_forward_grad(mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, const float *means3D, const float *shs,
+                               int32_t n_sh_coeffs, const float *colors_precomp, const float *opacities, const float *scales,
+                               const float *rotations, const float *cov3D_precomp, float *out_color, float *out_alpha,
+                               int32_t *radii) {
+  return forward_impl(r, s, n, means3D, shs, n_sh_coeffs, colors_precomp, opacities, scales, rotations, cov3D_precomp, out_color,
+                      out_alpha, radii, true);
+}
+
+int mpmhip_raster_saved_bytes(const mpmhip_raster *r, int64_t *bytes, int64_t *n_entries) {
+  if (!r || !bytes || !n_entries) return MPMHIP_ERR_INVALID;
+  if (!r->grad_frame) return MPMHIP_ERR_STATE;
+  *bytes = (int64_t)saved_layout((size_t)r->grad_n, (size_t)r->grad_tiles, r->grad_pixels, (size_t)r->grad_entries).bytes;
+  *n_entries = r->grad_entries;
+  return MPMHIP_OK;
+}
+
+int mpmhip_raster_save(mpmhip_raster *r, void *dst, int64_t bytes) {
+  if (!r || !dst) return MPMHIP_ERR_INVALID;
+  if (!r->grad_frame) return MPMHIP_ERR_STATE;
+  const size_t n = (size_t)r->grad_n, e = (size_t)r->grad_entries;
+  const SavedLayout l = saved_layout(n, (size_t)r->grad_tiles, r->grad_pixels, e);
+  if (bytes != (int64_t)l.bytes) return MPMHIP_ERR_INVALID;
+  RS_CHECK(hipSetDevice(r->device));
+  char *d = (char *)dst;
+  auto copy = [&](size_t at, const void *src, size_t size) {
+    return size == 0 ? MPMHIP_OK : check(hipMemcpyAsync(d + at, src, size, hipMemcpyDeviceToDevice, r->stream));
+  };
+  if (int rc = copy(l.rec0, r->rec0, n * sizeof(float4))) return rc;
+  if (int rc = copy(l.rec1, r->rec1, n * sizeof(float4))) return rc;
+  if (int rc = copy(l.rect, r->rect, n * sizeof(int4))) return rc;
+  if (int rc = copy(l.offsets, r->offsets, n ? (n + 1) * sizeof(uint64_t) : 0)) return rc;
+  if (int rc = copy(l.ranges, r->ranges, (size_t)r->grad_tiles * sizeof(uint2))) return rc;
+  if (int rc = copy(l.colour, r->colour, n * 3 * sizeof(float))) return rc;
+  if (int rc = copy(l.pix_T, r->pix_T, r->grad_pixels * sizeof(float))) return rc;
+  if (int rc = copy(l.pix_stop, r->pix_stop, r->grad_pixels * sizeof(uint32_t))) return rc;
+  if (int rc = copy(l.vals, r->vals[1], e * sizeof(uint32_t))) return rc;
+  if (int rc = copy(l.inv, r->inv, e * sizeof(uint32_t))) return rc;
+  return MPMHIP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+int forward_impl(mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, const float *means3D, const float *shs,
+                 int32_t n_sh_coeffs, const float *colors_precomp, const float *opacities, const float *scales,
+                 const float *rotations, const float *cov3D_precomp, float *out_color, float *out_alpha, int32_t *radii,
+                 const bool grad) {
   if (!r || !s || n < 0 || s->image_height <= 0 || s->image_width <= 0 || !out_color || !out_alpha) return MPMHIP_ERR_INVALID;
   if (!s->viewmatrix || !s->projmatrix || !s->campos) return MPMHIP_ERR_INVALID;
   if (n > 0) {
@@ -331,6 +318,7 @@ int mpmhip_raster_forward(mpmhip_raster *r, const mpmhip_raster_settings *s, int
   if (int rc = reserve_gaussians(r, n > 0 ? n : 1)) return rc;
   RS_CHECK(hipMemsetAsync(r->ranges, 0, (size_t)tiles * sizeof(uint2), st));
   r->last_n = n; r->last_tiles = tiles; r->last_entries = 0;
+  r->grad_frame = false;
 
   uint64_t total = 0;
   if (int rc = mark(r, 0)) return rc;
@@ -367,15 +355,30 @@ int mpmhip_raster_forward(mpmhip_raster *r, const mpmhip_raster_settings *s, int
     if (int rc = mark(r, 4)) return rc;
     hipLaunchKernelGGL(k_raster_ranges, blocks((int64_t)total), TPB, 0, st, (int64_t)total, (const uint64_t *)r->keys[1], r->ranges);
     RS_CHECK(hipGetLastError());
+    if (grad) {
+      if (int rc = reserve_grad(r, (size_t)W * H, (size_t)total)) return rc;
+      hipLaunchKernelGGL(k_raster_inverse, blocks((int64_t)total), TPB, 0, st, (int64_t)total, gx, (const uint64_t *)r->keys[1],
+                         (const uint32_t *)r->vals[1], (const int4 *)r->rect, (const uint64_t *)r->offsets, r->inv);
+      RS_CHECK(hipGetLastError());
+    }
   } else {
     if (int rc = mark(r, 3)) return rc;
     if (int rc = mark(r, 4)) return rc;
   }
   if (int rc = mark(r, 5)) return rc;
   r->last_entries = (int64_t)total;
-  hipLaunchKernelGGL(k_raster_render, dim3((unsigned)gx, (unsigned)gy), TPB, 0, st, W, H, gx, (const uint2 *)r->ranges,
-                     (const uint32_t *)r->vals[1], (const float4 *)r->rec0, (const float4 *)r->rec1, (const float *)r->colour,
-                     s->bg[0], s->bg[1], s->bg[2], out_color, out_alpha);
+  if (grad) {
+    if (int rc = reserve_grad(r, (size_t)W * H, 0)) return rc;
+    hipLaunchKernelGGL(k_raster_render<true>, dim3((unsigned)gx, (unsigned)gy), TPB, 0, st, W, H, gx, (const uint2 *)r->ranges,
+                       (const uint32_t *)r->vals[1], (const float4 *)r->rec0, (const float4 *)r->rec1, (const float *)r->colour,
+                       s->bg[0], s->bg[1], s->bg[2], out_color, out_alpha, r->pix_T, r->pix_stop);
+    r->grad_frame = true;
+    r->grad_n = n; r->grad_tiles = tiles; r->grad_pixels = (size_t)W * H; r->grad_entries = (int64_t)total;
+  } else {
+    hipLaunchKernelGGL(k_raster_render<false>, dim3((unsigned)gx, (unsigned)gy), TPB, 0, st, W, H, gx, (const uint2 *)r->ranges,
+                       (const uint32_t *)r->vals[1], (const float4 *)r->rec0, (const float4 *)r->rec1, (const float *)r->colour,
+                       s->bg[0], s->bg[1], s->bg[2], out_color, out_alpha, (float *)nullptr, (uint32_t *)nullptr);
+  }
   RS_CHECK(hipGetLastError());
   if (r->profile) {
     if (int rc = mark(r, 6)) return rc;
@@ -389,6 +392,10 @@ int mpmhip_raster_forward(mpmhip_raster *r, const mpmhip_raster_settings *s, int
   }
   return MPMHIP_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int mpmhip_raster_profile(mpmhip_raster *r, int32_t on, double *stage_ms, int64_t *frames) {
   if (!r) return MPMHIP_ERR_INVALID;
@@ -424,7 +431,8 @@ int mpmhip_raster_stats(const mpmhip_raster *r, mpmhip_raster_stats_t *out) {
   out->scratch_bytes = (int64_t)((size_t)r->cap_n * (2 * sizeof(float4) + 3 * sizeof(float) + sizeof(int4)) +
                                  ((size_t)r->cap_n + 1) * (sizeof(uint32_t) + sizeof(uint64_t)) + r->scan_tmp_bytes +
                                  r->cap_e * 2 * (sizeof(uint64_t) + sizeof(uint32_t)) + r->sort_tmp_bytes +
-                                 (size_t)r->cap_tiles * sizeof(uint2));
+                                 (size_t)r->cap_tiles * sizeof(uint2) + r->cap_pix * (sizeof(float) + sizeof(uint32_t)) +
+                                 r->cap_inv * sizeof(uint32_t) + r->cap_rows * sizeof(float));
   return MPMHIP_OK;
 }
 

@@ -1,0 +1,161 @@
+// raster_state.hpp -- what raster.hip (forward) and raster_backward.hip (backward) share: the handle, the layout of a saved
+// frame, and the small host helpers of both.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/mpmhip.h"
+#include "raster_grad_math.hpp"
+
+struct mpmhip_raster {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  // per Gaussian (capacity cap_n)
+  int cap_n = 0;
+  float4 *rec0 = nullptr, *rec1 = nullptr;  // (px, py, opacity, depth), (A, B, C, 0)
+  float *colour = nullptr;                  // [n*3]
+  int4 *rect = nullptr;                     // x0 y0 x1 y1
+  uint32_t *touched = nullptr;              // [n + 1], the last one 0
+  uint64_t *offsets = nullptr;              // [n + 1] exclusive scan; offsets[n] = number of entries
+  void *scan_tmp = nullptr;
+  size_t scan_tmp_bytes = 0;
+  // per (tile, Gaussian) entry (capacity cap_e)
+  size_t cap_e = 0;
+  uint64_t *keys[2] = {nullptr, nullptr};
+  uint32_t *vals[2] = {nullptr, nullptr};
+  void *sort_tmp = nullptr;
+  size_t sort_tmp_bytes = 0;
+  // per tile (capacity cap_tiles)
+  int cap_tiles = 0;
+  uint2 *ranges = nullptr;
+  // small
+  uint64_t *h_total = nullptr;  // pinned
+  int32_t *d_counts = nullptr;  // [2]: longest tile list, Gaussians with radius > 0 (mpmhip_raster_stats)
+  // the last frame, for mpmhip_raster_stats
+  int64_t last_entries = 0;
+  int last_n = 0, last_tiles = 0;
+  // Training flavour (mpmhip_raster_forward_grad / _save / _backward); nothing here is allocated before the first such call.
+  size_t cap_pix = 0;
+  float *pix_T = nullptr;        // per pixel: the final T itself (1 - alpha_out has lost the bits)
+  uint32_t *pix_stop = nullptr;  // per pixel: the entry that finished it, or the end of its tile's range
+  size_t cap_inv = 0;
+  uint32_t *inv = nullptr;       // entry position before the sort (offsets[g] + place in g's rectangle) -> sorted position
+  bool grad_frame = false;       // the newest frame recorded its per-pixel state: _save may copy it
+  int grad_n = 0, grad_tiles = 0;
+  size_t grad_pixels = 0;
+  int64_t grad_entries = 0;
+  size_t cap_rows = 0;
+  float *rows = nullptr;         // the backward pass's own temporary: [entries][N_PARTIALS]
+  // mpmhip_raster_profile: events between the stages of a frame (off by default: no events, no extra synchronisation)
+  bool profile = false;
+  hipEvent_t ev[MPMHIP_RASTER_STAGES + 1] = {};
+  double stage_ms[MPMHIP_RASTER_STAGES] = {};
+  int64_t profiled_frames = 0;
+};
+
+namespace raster_host {
+
+constexpr int TPB = 256;
+constexpr int TILE = rast::TILE;
+static_assert(TILE * TILE == TPB, "one lane per pixel of a tile");
+
+struct Camera {  // the scalar half of mpmhip_raster_settings plus its three device pointers
+  int W, H, gx, gy;
+  float tanfovx, tanfovy, scale_modifier;
+  int sh_degree;
+  const float *view, *proj, *campos;
+};
+
+// A saved frame (mpmhip_raster_save): everything the backward pass reads of the forward one, copied out of the handle's
+// scratch, which the next forward overwrites.  Offsets in bytes, every section 16-byte aligned but the last two.
+struct SavedLayout {
+  size_t rec0, rec1, rect, offsets, ranges, colour, pix_T, pix_stop, vals, inv, bytes;
+};
+inline SavedLayout saved_layout(size_t n, size_t tiles, size_t pixels, size_t entries) {
+  auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  SavedLayout l;
+  size_t at = 0;
+  l.rec0 = at; at += n * sizeof(float4);
+  l.rec1 = at; at += n * sizeof(float4);
+  l.rect = at; at += n * sizeof(int4);
+  l.offsets = at; at = up(at + (n + 1) * sizeof(uint64_t));
+  l.ranges = at; at = up(at + tiles * sizeof(uint2));
+  l.colour = at; at = up(at + n * 3 * sizeof(float));
+  l.pix_T = at; at = up(at + pixels * sizeof(float));
+  l.pix_stop = at; at = up(at + pixels * sizeof(uint32_t));
+  l.vals = at; at += entries * sizeof(uint32_t);
+  l.inv = at; at += entries * sizeof(uint32_t);
+  l.bytes = at;
+  return l;
+}
+
+inline int check(hipError_t e) { return e == hipSuccess ? MPMHIP_OK : MPMHIP_ERR_HIP; }
+#define RS_CHECK(expr) do { if (int rc_ = check(expr)) return rc_; } while (0)
+
+inline unsigned blocks(int64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
+
+template <class T>
+inline int regrow(T *&p, size_t count) {
+  if (p) RS_CHECK(hipFree(p));
+  p = nullptr;
+  return check(hipMalloc((void **)&p, count * sizeof(T)));
+}
+
+// capacity that holds `need`: at least twice the old one, so that a slowly growing scene reallocates O(log) times
+template <class I>
+inline I grown(I cap, I need) { return need > 2 * cap ? need : 2 * cap; }
+
+// temporary storage of a rocPRIM call: asked for with the call's own arguments every frame (a host-side computation)
+inline int reserve_tmp(mpmhip_raster *r, void *&p, size_t &have, size_t need) {
+  if (need <= have) return MPMHIP_OK;
+  RS_CHECK(hipStreamSynchronize(r->stream));
+  const size_t cap = grown(have, need);
+  char *tmp = (char *)p;
+  p = nullptr;
+  have = 0;
+  if (int rc = regrow(tmp, cap)) return rc;
+  p = tmp;
+  have = cap;
+  return MPMHIP_OK;
+}
+
+inline int reserve_gaussians(mpmhip_raster *r, int n) {
+  if (n <= r->cap_n) return MPMHIP_OK;
+  RS_CHECK(hipStreamSynchronize(r->stream));  // nothing in flight may still read what is freed
+  const int cap = grown(r->cap_n, n);
+  r->cap_n = 0;
+  if (int rc = regrow(r->rec0, (size_t)cap)) return rc;
+  if (int rc = regrow(r->rec1, (size_t)cap)) return rc;
+  if (int rc = regrow(r->colour, (size_t)cap * 3)) return rc;
+  if (int rc = regrow(r->rect, (size_t)cap)) return rc;
+  if (int rc = regrow(r->touched, (size_t)cap + 1)) return rc;
+  if (int rc = regrow(r->offsets, (size_t)cap + 1)) return rc;
+  r->cap_n = cap;
+  return MPMHIP_OK;
+}
+
+inline int reserve_entries(mpmhip_raster *r, size_t total) {
+  if (total <= r->cap_e) return MPMHIP_OK;
+  RS_CHECK(hipStreamSynchronize(r->stream));
+  const size_t cap = grown(r->cap_e, total);
+  r->cap_e = 0;
+  for (int k = 0; k < 2; ++k) {
+    if (int rc = regrow(r->keys[k], cap)) return rc;
+    if (int rc = regrow(r->vals[k], cap)) return rc;
+  }
+  r->cap_e = cap;
+  return MPMHIP_OK;
+}
+
+inline int reserve_tiles(mpmhip_raster *r, int tiles) {
+  if (tiles <= r->cap_tiles) return MPMHIP_OK;
+  RS_CHECK(hipStreamSynchronize(r->stream));
+  const int cap = grown(r->cap_tiles, tiles);
+  r->cap_tiles = 0;
+  if (int rc = regrow(r->ranges, (size_t)cap)) return rc;
+  r->cap_tiles = cap;
+  return MPMHIP_OK;
+}
+
+}  // namespace raster_host

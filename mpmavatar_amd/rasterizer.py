@@ -1,4 +1,4 @@
-"""Forward Gaussian rasteriser on the GPU behind the names of the reference's ``diff_gauss`` extension
+"""Gaussian rasteriser on the GPU, forward and backward, behind the names of the reference's ``diff_gauss`` extension
 (/root/reference/gaussian_renderer/__init__.py:14,36-103): the last step of the chain solver -> ``MeshFrames`` ->
 ``BoundGaussians.render_inputs`` -> image,
 
@@ -8,12 +8,32 @@
                                              campos=cam.camera_center, prefiltered=False, debug=False)
     image, _, _, mask, radii, _ = GaussianRasterizer(raster_settings=settings)(**gaussians.render_inputs(frames, ...))
 
-over the HIP pipeline of ``csrc/raster.hip`` (``mpmhip_raster_forward``).  With ``mpmavatar_amd/compat`` on PYTHONPATH the
-reference's ``from diff_gauss import GaussianRasterizationSettings, GaussianRasterizer`` resolves to these two names.
+over the HIP pipelines of ``csrc/raster.hip`` (forward) and ``csrc/raster_backward.hip`` (backward).  With
+``mpmavatar_amd/compat`` on PYTHONPATH the reference's ``from diff_gauss import GaussianRasterizationSettings,
+GaussianRasterizer`` resolves to these two names.
 
-FORWARD ONLY.  There is no backward pass: ``requires_grad`` on inputs such as ``means2D`` is accepted and ignored, and the
-outputs carry no graph.  The eval loop (train_material_params.py:857-872) and the demo (run_demo.py:540-604) need no more;
-``train_appearance.py``, which optimises the Gaussians through the renderer, cannot use it.
+FORWARD AND BACKWARD.  With grad mode on and at least one of ``means3D``, ``opacities``, ``shs``, ``colors_precomp``,
+``scales``, ``rotations``, ``cov3Ds_precomp`` requiring grad, ``image`` and ``alpha`` carry a graph, and ``loss.backward()``
+-- the render call and loss of ``train_appearance.py`` (:123-155: image * mask, L1 + SSIM + LPIPS) -- fills the gradients of
+those inputs and of ``means2D`` (``viewspace_point_tensor.grad`` of train_appearance.py:245-253; the published convention:
+dL/dpx * W/2, dL/dpy * H/2, 0 -- the gradient with respect to an additive NDC offset of the pixel centre; the tensor's value
+stays ignored).  ``means2D`` requiring grad ALONE builds no graph: that is how the eval loop
+(train_material_params.py:857-872) and the demo (run_demo.py:540-604) call it, and they get exactly the forward-only call:
+same kernels, nothing more allocated.  ``radii`` is non-differentiable; the camera tensors, ``bg`` and ``scale_modifier``
+get no gradient; there is no double backward.
+
+The gradient is the exact derivative of the forward function as computed here (``csrc/raster_grad_math.hpp``), every
+discrete decision held fixed: culling, radius and tile rectangle, depth order, power > 0, alpha < 1/255, the T < 1e-4
+finish.  The clamps differentiate as clamps, zero slope where they bind: alpha = min(0.99, .), the +-1.3 tanfov clamp inside
+the Jacobian, max(0, sh + 0.5).  ONE DEVIATION, unconfirmed: the CUDA original is remembered to let the gradient through a
+bound 0.99 alpha clamp; its source is not at hand to check.  Here a bound clamp returns zero to the opacity and the
+geometry, because that is the derivative of what the forward pass computes.  No floating-point atomics: two backward
+passes over the same inputs return the same bits.
+
+A frame that will be differentiated keeps its own copy of the pipeline's state (packed records, sorted indices, tile ranges,
+per-pixel T and stopping position) in a tensor held by the autograd node: the scratch is shared by every rasteriser on a
+device and stream, and the next forward overwrites it.  What is NOT differentiable: ``BoundGaussians.render_inputs`` is a
+forward-only launch, so gradients stop at its outputs; densification itself is the caller's.
 
 Each call blocks the host once (the pipeline reads one count back to size its sort, csrc/raster.hip).  The three floats of
 ``bg`` are read from the device the first time a given tensor is seen and kept until it is modified in place or freed, so
@@ -108,10 +128,76 @@ def look_at_camera(eye, target, fov_deg, device, znear=0.01, zfar=100.0):
     return f32(w2c.T), f32(w2c.T @ P.T), f32(eye), t
 
 
+class _Frame:
+    """What one differentiable call keeps besides its input tensors: the settings struct with the camera tensors it points
+    to, the handle, and the saved state of the pipeline (a uint8 tensor this frame owns)."""
+    __slots__ = ("cs", "keep", "hd", "n", "n_sh", "saved", "n_entries", "h", "w")
+
+
+class _Rasterize(torch.autograd.Function):
+    """forward: mpmhip_raster_forward_grad + mpmhip_raster_save; backward: mpmhip_raster_backward"""
+
+    @staticmethod
+    def forward(ctx, fr, means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3Ds_precomp):
+        hd, dev = fr.hd, means3D.device
+        image = torch.empty(3, fr.h, fr.w, dtype=torch.float32, device=dev)
+        alpha = torch.empty(1, fr.h, fr.w, dtype=torch.float32, device=dev)
+        radii = torch.empty(fr.n, dtype=torch.int32, device=dev)
+        p = _ptr
+        rc = hd.lib.mpmhip_raster_forward_grad(hd.ptr, C.byref(fr.cs), fr.n, p(means3D), p(shs), fr.n_sh, p(colors_precomp), p(opacities),
+                                               p(scales), p(rotations), p(cov3Ds_precomp), image.data_ptr(), alpha.data_ptr(), p(radii))
+        if rc != L.OK:
+            raise L.MPMHipError(rc, "mpmhip_raster_forward_grad failed")
+        size, entries = C.c_int64(), C.c_int64()
+        rc = hd.lib.mpmhip_raster_saved_bytes(hd.ptr, C.byref(size), C.byref(entries))
+        if rc != L.OK:
+            raise L.MPMHipError(rc, "mpmhip_raster_saved_bytes failed")
+        fr.saved = torch.empty(size.value, dtype=torch.uint8, device=dev)
+        fr.n_entries = entries.value
+        rc = hd.lib.mpmhip_raster_save(hd.ptr, fr.saved.data_ptr(), size.value)
+        if rc != L.OK:
+            raise L.MPMHipError(rc, "mpmhip_raster_save failed")
+        ctx.fr = fr
+        ctx.means2D_shape = None if means2D is None else tuple(means2D.shape)
+        ctx.save_for_backward(means3D, opacities, shs, colors_precomp, scales, rotations, cov3Ds_precomp)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)       # an unused output's gradient arrives as None and goes down as NULL = zeros
+        return image, alpha, radii
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_image, g_alpha, _g_radii):
+        fr = ctx.fr
+        means3D, opacities, shs, colors_precomp, scales, rotations, cov3Ds_precomp = ctx.saved_tensors
+        hd, dev, n = fr.hd, means3D.device, fr.n
+        grad_in = lambda g, shape: None if g is None else g.to(torch.float32).expand(shape).contiguous()
+        g_image, g_alpha = grad_in(g_image, (3, fr.h, fr.w)), grad_in(g_alpha, (1, fr.h, fr.w))
+        like = lambda t: None if t is None else torch.empty_like(t)
+        d_means3D, d_means2D, d_opac = torch.empty_like(means3D), torch.empty(n, 3, dtype=torch.float32, device=dev), torch.empty_like(opacities)
+        d_shs, d_col, d_scales, d_rots, d_cov = like(shs), like(colors_precomp), like(scales), like(rotations), like(cov3Ds_precomp)
+        p = _ptr
+        rc = hd.lib.mpmhip_raster_backward(hd.ptr, C.byref(fr.cs), n, p(means3D), p(shs), fr.n_sh, p(colors_precomp), p(opacities), p(scales),
+                                           p(rotations), p(cov3Ds_precomp), fr.saved.data_ptr(), fr.saved.numel(), fr.n_entries,
+                                           p(g_image), p(g_alpha), p(d_means3D), p(d_means2D), p(d_shs), p(d_col), p(d_opac),
+                                           p(d_scales), p(d_rots), p(d_cov))
+        if rc != L.OK:
+            raise L.MPMHipError(rc, "mpmhip_raster_backward failed")
+        if ctx.means2D_shape is None or not ctx.needs_input_grad[2]:
+            d_means2D = None
+        elif ctx.means2D_shape != (n, 3):
+            raise RuntimeError(f"means2D: expected shape {(n, 3)} to receive its gradient, got {ctx.means2D_shape}")
+        return None, d_means3D, d_means2D, d_opac, d_shs, d_col, d_scales, d_rots, d_cov
+
+
+def _ptr(t):
+    return None if t is None or t.numel() == 0 else t.data_ptr()
+
+
 class GaussianRasterizer:
     """``GaussianRasterizer(raster_settings)(means3D=, means2D=, shs=, colors_precomp=, opacities=, scales=, rotations=,
     cov3Ds_precomp=)`` -> ``(image [3, H, W], None, None, alpha [1, H, W], radii [N] int32, None)``: the 6-tuple of the
-    reference's call, of which it reads slots 0, 3 and 4 (gaussian_renderer/__init__.py:95).  Forward only (module docstring)."""
+    reference's call, of which it reads slots 0, 3 and 4 (gaussian_renderer/__init__.py:95).  image and alpha carry a graph when
+    an input other than means2D requires grad (module docstring)."""
 
     def __init__(self, raster_settings: GaussianRasterizationSettings, private_scratch: bool = False):
         """The reference builds a new rasteriser for every frame (gaussian_renderer/__init__.py:51), so the scratch is shared
@@ -158,6 +244,10 @@ class GaussianRasterizer:
                         ("scales", scales), ("rotations", rotations), ("cov3Ds_precomp", cov3Ds_precomp)):
             if t is not None and not isinstance(t, torch.Tensor):
                 raise RuntimeError(f"{name}: expected a tensor")
+        given = dict(means3D=means3D, opacities=opacities, shs=shs, colors_precomp=colors_precomp, scales=scales, rotations=rotations,
+                     cov3Ds_precomp=cov3Ds_precomp)
+        # means2D requiring grad alone builds no graph: the eval loop passes it so and reads no gradient
+        graph = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in given.values())
         with torch.no_grad():
             m = _chk(means3D.detach(), torch.float32, "means3D")
             if m.dim() != 2 or m.shape[1] != 3:
@@ -194,16 +284,25 @@ class GaussianRasterizer:
             bg3 = _bg_floats(bg)
             cs = L.RasterSettings(h, w, float(s.tanfovx), float(s.tanfovy), L.f3(*bg3), float(s.scale_modifier), deg,
                                   view.data_ptr(), proj.data_ptr(), campos.data_ptr())
-            image = torch.empty(3, h, w, dtype=torch.float32, device=dev)
-            alpha = torch.empty(1, h, w, dtype=torch.float32, device=dev)
-            radii = torch.empty(n, dtype=torch.int32, device=dev)
             hd = self._handle(dev)
-            p = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
-            rc = hd.lib.mpmhip_raster_forward(hd.ptr, C.byref(cs), n, p(m), p(shs), n_sh, p(colors_precomp), p(op), p(scales),
-                                              p(rotations), p(cov3Ds_precomp), image.data_ptr(), alpha.data_ptr(), p(radii))
-            if rc != L.OK:
-                raise L.MPMHipError(rc, "mpmhip_raster_forward failed")
-            self._last, hd.last_user = hd, weakref.ref(self)
+            if not graph:
+                image = torch.empty(3, h, w, dtype=torch.float32, device=dev)
+                alpha = torch.empty(1, h, w, dtype=torch.float32, device=dev)
+                radii = torch.empty(n, dtype=torch.int32, device=dev)
+                p = _ptr
+                rc = hd.lib.mpmhip_raster_forward(hd.ptr, C.byref(cs), n, p(m), p(shs), n_sh, p(colors_precomp), p(op), p(scales),
+                                                  p(rotations), p(cov3Ds_precomp), image.data_ptr(), alpha.data_ptr(), p(radii))
+                if rc != L.OK:
+                    raise L.MPMHipError(rc, "mpmhip_raster_forward failed")
+                self._last, hd.last_user = hd, weakref.ref(self)
+                return image, None, None, alpha, radii, None
+        # the validated values above are detached views of these: the same memory, now with the graph's leaves attached
+        fr = _Frame()
+        fr.cs, fr.keep, fr.hd, fr.n, fr.n_sh, fr.h, fr.w = cs, (view, proj, campos), hd, n, n_sh, h, w
+        m2 = means2D if isinstance(means2D, torch.Tensor) and means2D.requires_grad else None
+        image, alpha, radii = _Rasterize.apply(fr, given["means3D"], m2, given["opacities"], given["shs"], given["colors_precomp"],
+                                               given["scales"], given["rotations"], given["cov3Ds_precomp"])
+        self._last, hd.last_user = hd, weakref.ref(self)
         return image, None, None, alpha, radii, None
 
     __call__ = forward

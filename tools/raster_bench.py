@@ -3,10 +3,16 @@
 the S3 garment (scenes.garment_cylinder, 79,600 faces) at 1024 x 1024, 20 warm-up and 100 timed frames.
 
     python tools/raster_bench.py [--gaussians 200000] [--size 1024] [--warmup 20] [--frames 100] [--out file.json]
+    python tools/raster_bench.py --backward [...]      the backward pass on the same frame -> profiles/raster_bench_backward.json
 
 Reported: milliseconds per frame of the whole call (HIP events on torch's current stream around the timed frames, frames
 + render_inputs + rasteriser, and the rasteriser alone), and per stage of the pipeline from the library's own event brackets
-(mpmhip_raster_profile, a second pass: the brackets make every frame wait for its end)."""
+(mpmhip_raster_profile, a second pass: the brackets make every frame wait for its end).
+
+--backward times, each stage over the timed frames between two HIP events, the plain forward call, the forward call that
+records its state (mpmhip_raster_forward_grad), the copy of that state (mpmhip_raster_save) and the backward pass
+(mpmhip_raster_backward with both incoming gradients), and reports backward / forward and the traffic of the per-entry row
+buffer: 36 B per (tile, Gaussian) entry written once and read once, over the backward pass's time."""
 import argparse
 import ctypes as C
 import json
@@ -37,6 +43,63 @@ def events_ms(fn, reps):
     return e0.elapsed_time(e1) / reps
 
 
+def backward_mode(a, rast, args, settings, dev, n, n_f):
+    h = w = a.size
+    hd = rast._handle(dev)
+    lib = hd.lib
+    view, proj, campos = settings.viewmatrix.contiguous(), settings.projmatrix.contiguous(), settings.campos.contiguous()
+    cs = L.RasterSettings(h, w, settings.tanfovx, settings.tanfovy, L.f3(0.0, 0.0, 0.0), 1.0, 0, view.data_ptr(), proj.data_ptr(),
+                          campos.data_ptr())
+    t = {k: args[k].detach().contiguous() for k in ("means3D", "colors_precomp", "opacities", "scales", "rotations")}
+    image, alpha = torch.empty(3, h, w, device=dev), torch.empty(1, h, w, device=dev)
+    radii = torch.empty(n, dtype=torch.int32, device=dev)
+    fwd = (hd.ptr, C.byref(cs), n, t["means3D"].data_ptr(), None, 0, t["colors_precomp"].data_ptr(), t["opacities"].data_ptr(),
+           t["scales"].data_ptr(), t["rotations"].data_ptr(), None, image.data_ptr(), alpha.data_ptr(), radii.data_ptr())
+
+    def ok(rc):
+        if rc != L.OK:
+            raise L.MPMHipError(rc, "raster call failed")
+
+    ok(lib.mpmhip_raster_forward_grad(*fwd))
+    size, entries = C.c_int64(), C.c_int64()
+    ok(lib.mpmhip_raster_saved_bytes(hd.ptr, C.byref(size), C.byref(entries)))
+    saved = torch.empty(size.value, dtype=torch.uint8, device=dev)
+    g = torch.Generator(device=dev).manual_seed(1)
+    g_image, g_alpha = torch.randn(3, h, w, device=dev, generator=g), torch.randn(1, h, w, device=dev, generator=g)
+    d = {k: torch.empty_like(v) for k, v in t.items()}
+    d["means2D"] = torch.empty(n, 3, device=dev)
+    bwd = fwd[:11] + (saved.data_ptr(), size.value, entries.value, g_image.data_ptr(), g_alpha.data_ptr(), d["means3D"].data_ptr(),
+                      d["means2D"].data_ptr(), None, d["colors_precomp"].data_ptr(), d["opacities"].data_ptr(), d["scales"].data_ptr(),
+                      d["rotations"].data_ptr(), None)
+    stages = {"forward": lambda: ok(lib.mpmhip_raster_forward(*fwd)), "forward_with_state": lambda: ok(lib.mpmhip_raster_forward_grad(*fwd)),
+              "save": lambda: ok(lib.mpmhip_raster_save(hd.ptr, saved.data_ptr(), size.value)), "backward": lambda: ok(lib.mpmhip_raster_backward(*bwd))}
+    ok(lib.mpmhip_raster_save(hd.ptr, saved.data_ptr(), size.value))
+    ms = {}
+    for name, fn in stages.items():
+        if name == "save":
+            ok(lib.mpmhip_raster_forward_grad(*fwd))       # the state to copy is the newest frame's
+        for _ in range(a.warmup):
+            fn()
+        ms[name] = events_ms(fn, a.frames)
+    first = {k: v.clone() for k, v in d.items()}
+    ok(lib.mpmhip_raster_backward(*bwd))
+    torch.cuda.synchronize()
+    row_bytes = 36 * entries.value
+    res = {"gaussians": n, "faces": n_f, "image": [h, w], "warmup": a.warmup, "frames": a.frames, "stage_ms": ms,
+           "backward_over_forward": ms["backward"] / ms["forward"], "training_frame_ms": ms["forward_with_state"] + ms["save"] + ms["backward"],
+           "n_entries": entries.value, "saved_bytes": size.value, "row_buffer_bytes": row_bytes,
+           "row_buffer_bytes_per_s_over_backward": 2 * row_bytes / (ms["backward"] * 1e-3),
+           "finite": bool(all(torch.isfinite(v).all() for v in d.values())),
+           "bitwise_repeatable": bool(all(torch.equal(first[k], d[k]) for k in d)),
+           "grad_abs_max": {k: float(v.abs().max()) for k, v in d.items()}}
+    line = json.dumps(res)
+    print(line)
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "raster_bench_backward.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gaussians", type=int, default=200000)
@@ -44,6 +107,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--frames", type=int, default=100)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--backward", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("raster_bench.py measures on the GPU; there is none")
@@ -76,6 +140,9 @@ def main():
         inputs()
         render()
 
+    if a.backward:
+        inputs()
+        return backward_mode(a, rast, state["args"], settings, dev, n, int(n_f))
     for _ in range(a.warmup):
         frame()
     frame_ms = events_ms(frame, a.frames)
