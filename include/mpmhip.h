@@ -409,7 +409,8 @@ int mpmhip_raster_forward(mpmhip_raster *r, const mpmhip_raster_settings *s, int
                           int32_t *radii);
 /* ---- the rasteriser's backward pass: what train_appearance.py:123-155 needs ---------------------------------------------
  * There the render call (gaussian_renderer/__init__.py:95-103 with override_color, scales and rotations) is followed by
- * image * mask, L1 + SSIM + LPIPS and loss.backward() (train_appearance.py:123-155), and viewspace_point_tensor.grad -- the
+ * image * mask, the loss (L1 + SSIM: mpmhip_image_loss_* below; LPIPS: the caller's) and loss.backward()
+ * (train_appearance.py:123-155), and viewspace_point_tensor.grad -- the
  * gradient of means2D -- feeds the densification statistics (train_appearance.py:245-253).  The gradient is the exact
  * derivative of the forward function above with every discrete decision held fixed (culling, radius, tile rectangle, depth
  * order, power > 0, alpha < 1/255, the T < 1e-4 finish); the clamps -- alpha = min(0.99, .), the frustum clamp inside the
@@ -455,6 +456,36 @@ int mpmhip_raster_stats(const mpmhip_raster *r, mpmhip_raster_stats_t *out);
  * summed over `frames` frames; either may be NULL); switching from off to on then resets the sums. */
 #define MPMHIP_RASTER_STAGES 6
 int mpmhip_raster_profile(mpmhip_raster *r, int32_t on, double *stage_ms, int64_t *frames);
+
+/* ---- after the rasteriser: the image loss and the image metrics ----------------------------------------------------------
+ * What stands between the render call and loss.backward() in train_appearance.py:132-134 -- (1 - lambda) l1_loss(image, gt)
+ * + lambda (1 - ssim(image, gt)), utils/loss_utils.py:18-64 -- and what eval.py:89-91 closes every run with: psnr
+ * (utils/image_utils.py:17-19) and ssim.  LPIPS (train_appearance.py:133, eval.py:89) needs network weights and stays the
+ * caller's.  Stand-alone maps on [dev] arrays (no context; `stream` is a hipStream_t, NULL = default stream); nothing here
+ * allocates or synchronises, every buffer is the caller's.  A "plane" is one (batch, channel) image of H x W floats;
+ * planes = N * C, planes stored one after the other.  Both return MPMHIP_ERR_INVALID, with nothing launched, for a NULL
+ * required pointer, planes, H or W <= 0, or planes * H * W > 2^31 - 1.  All arithmetic fp32 with the sums in fp64 in a fixed
+ * order, no floating-point atomics: the same input gives the same bits.
+ *
+ * mpmhip_image_loss_forward: torch.abs(img - gt).mean() (loss_utils.py:18-19), ((img - gt) ** 2).mean() (the mse of
+ * image_utils.py:18) and _ssim(...).mean() (loss_utils.py:44-62: the 11-tap Gaussian window of :24-32, sigma 1.5, zero padding
+ * of 5, C1 = 0.01^2, C2 = 0.03^2, variances as E[x^2] - mu^2 in fp32 as there), each PER PLANE:
+ * out_means [planes*3] = mean |d|, mean d^2, mean SSIM map of plane 0, then of plane 1, ...  The reference's means over
+ * planes, 1 - ssim, the lambda mix and 20 log10(1 / sqrt(mse)) are the caller's few scalar operations.
+ * maps [planes*3*H*W] or NULL: per plane three H x W planes, the partial derivatives of the SSIM map value with respect to
+ * mu1 (in total), sigma1^2 and sigma12 at every pixel, which the backward pass convolves; NULL (evaluation) stores nothing.
+ * scratch [MPMHIP_IMAGE_LOSS_SCRATCH(planes, H, W)] doubles: one triple per 16 x 16 tile. */
+#define MPMHIP_IMAGE_LOSS_SCRATCH(planes, H, W) ((int64_t)(planes) * (((H) + 15) / 16) * (((W) + 15) / 16) * 3)
+int mpmhip_image_loss_forward(int32_t device, void *stream, const float *img, const float *gt, int32_t planes, int32_t H, int32_t W,
+                              float *maps, double *scratch, float *out_means);
+/* What autograd does for loss.backward() through the expressions above (train_appearance.py:155), for img alone (gt gets no
+ * gradient): with the upstream gradients of the three per-plane means, g_l1, g_mse, g_ssim [planes] on the device (no value
+ * passes through the host),
+ *   d_img(q) = (g_l1[p] sign(x - y) + g_mse[p] 2 (x - y) + g_ssim[p] dSSIM(q)) / (H W),   sign(0) = 0 as torch's abs backward,
+ *   dSSIM(q) = (w * d_mu)(q) + 2 x(q) (w * d_s1)(q) + y(q) (w * d_s12)(q),   w * . the zero-padded window convolution of the
+ * maps that mpmhip_image_loss_forward stored for the same img and gt.  d_img [planes*H*W]: every element is written. */
+int mpmhip_image_loss_backward(int32_t device, void *stream, const float *img, const float *gt, int32_t planes, int32_t H, int32_t W,
+                               const float *maps, const float *g_l1, const float *g_mse, const float *g_ssim, float *d_img);
 
 /* ---- introspection ---------------------------------------------------------------------- */
 /* dense reference-layout copies of grid_m [G^3], grid_v_in [G^3*3], grid_v_out [G^3*3] as they
