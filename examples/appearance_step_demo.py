@@ -1,0 +1,108 @@
+#!/usr/bin/env python
+"""One appearance-training loop on the device, the call sequence of the reference's train_appearance.py:97-160 without its dataset:
+
+    per step:  verts = verts_orig + verts_offset            (select_mesh_by_timestep, scene/mesh_gaussian_model.py:122-134)
+               frames.set_mesh_by_verts(verts)              -> mpmhip_face_frames
+               args = gaussians.render_inputs(frames, ...)  -> mpmhip_render_inputs
+               image = GaussianRasterizer(settings)(**args) -> mpmhip_raster_forward_grad
+               loss, Ll1, ssim = image_loss(image, target)  -> mpmhip_image_loss_forward
+               loss.backward()                              -> image loss, rasteriser, binding and face-frame backward kernels
+               optimizer.step()                             (torch.optim.Adam, as the reference)
+
+    python examples/appearance_step_demo.py [--steps 30] [--size 64]
+
+The mesh is a 320-face icosphere with two Gaussians per face.  The target image is rendered from perturbed parameters and perturbed
+vertices; Adam then moves ``_xyz``, ``_rotation``, ``_scaling``, ``_opacity`` and a per-vertex ``verts_offset`` towards it, and the
+loss it prints falls.  Colours are fixed (``override_color``): ``convert_SH`` and the shadow network stay in torch in the reference too.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from mpmavatar_amd import garment  # noqa: E402
+from mpmavatar_amd.image_loss import image_loss  # noqa: E402
+from mpmavatar_amd.mesh_frames import MeshFrames  # noqa: E402
+from mpmavatar_amd.rasterizer import GaussianRasterizationSettings, GaussianRasterizer, look_at_camera  # noqa: E402
+from mpmavatar_amd.render_inputs import BoundGaussians  # noqa: E402
+
+PER_FACE = 2
+
+
+class Scene:
+    """Everything one training step needs; ``params`` are the five leaves the optimiser moves."""
+
+    def __init__(self, size=64, device="cuda:0", seed=0, eye=(0.0, 0.3, -2.0)):
+        dev = torch.device(device)
+        g = torch.Generator(device="cpu").manual_seed(seed)
+        rnd = lambda *s: torch.randn(*s, generator=g)
+        verts, faces = garment.icosphere(2, 0.5, (0.0, 0.0, 0.0))
+        self.verts_orig = torch.tensor(np.asarray(verts, np.float32), device=dev)
+        self.frames = MeshFrames(torch.tensor(np.asarray(faces, np.int32), device=dev))
+        n_f = faces.shape[0]
+        n = PER_FACE * n_f
+        binding = torch.arange(n_f, dtype=torch.int32).repeat_interleave(PER_FACE).to(dev)
+        # the parameters the target image was rendered from, and the perturbed ones training starts at
+        true = {"_xyz": 0.3 * rnd(n, 3) * torch.tensor([1.0, 1.0, 0.05]), "_rotation": rnd(n, 4), "_scaling": -0.7 + 0.2 * rnd(n, 3),
+                "_opacity": 1.5 + rnd(n, 1)}
+        start = {"_xyz": true["_xyz"] + 0.1 * rnd(n, 3), "_rotation": true["_rotation"] + 0.3 * rnd(n, 4),
+                 "_scaling": true["_scaling"] + 0.3 * rnd(n, 3), "_opacity": true["_opacity"] + rnd(n, 1)}
+        true_offset = 0.01 * rnd(*self.verts_orig.shape)
+        centre = self.verts_orig[self.frames.faces.long()].mean(1)[binding.long()]
+        self.colors = (0.5 + centre / (2 * centre.norm(dim=1, keepdim=True))).contiguous()       # colour by direction, fixed
+        view, proj, campos, tanfov = look_at_camera(np.array(eye, np.float64), np.zeros(3), 40.0, dev)
+        self.settings = GaussianRasterizationSettings(image_height=size, image_width=size, tanfovx=tanfov, tanfovy=tanfov,
+                                                      bg=torch.ones(3, device=dev), scale_modifier=1.0, viewmatrix=view, projmatrix=proj,
+                                                      sh_degree=0, campos=campos, prefiltered=False, debug=False)
+        no_sh = (torch.zeros(n, 1, 3, device=dev), torch.zeros(n, 0, 3, device=dev))
+        with torch.no_grad():
+            self.verts_offset = true_offset.to(dev)
+            self.gaussians = BoundGaussians(*[true[k].to(dev).contiguous() for k in ("_xyz", "_rotation", "_scaling", "_opacity")], *no_sh, binding)
+            self.target = self.render()[0]
+        self.verts_offset = torch.nn.Parameter(torch.zeros_like(self.verts_orig))
+        leaves = [torch.nn.Parameter(start[k].to(dev).contiguous()) for k in ("_xyz", "_rotation", "_scaling", "_opacity")]
+        self.gaussians = BoundGaussians(*leaves, *no_sh, binding)
+        self.params = dict(zip(("_xyz", "_rotation", "_scaling", "_opacity"), leaves), verts_offset=self.verts_offset)
+
+    def render(self):
+        """-> (image [3, size, size], radii [n]) from the current parameters"""
+        self.frames.set_mesh_by_verts(self.verts_orig + self.verts_offset)
+        args = self.gaussians.render_inputs(self.frames, override_color=self.colors)
+        image, _, _, _, radii, _ = GaussianRasterizer(raster_settings=self.settings)(**args)
+        return image, radii
+
+    def loss(self):
+        """-> (loss, radii): train_appearance.py:132,134 without the LPIPS term"""
+        image, radii = self.render()
+        return image_loss(image, self.target, 0.2)[0], radii
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--size", type=int, default=64)
+    a = ap.parse_args(argv)
+    sc = Scene(a.size)
+    lr = {"_xyz": 5e-3, "_rotation": 1e-2, "_scaling": 1e-2, "_opacity": 2e-2, "verts_offset": 1e-3}
+    opt = torch.optim.Adam([{"params": [p], "lr": lr[k], "name": k} for k, p in sc.params.items()], eps=1e-15)
+    losses = []
+    for step in range(a.steps + 1):
+        opt.zero_grad(set_to_none=True)
+        loss, radii = sc.loss()
+        losses.append(float(loss.detach()))
+        if step % 5 == 0:
+            print(f"step {step:3d}  loss {losses[-1]:.6f}  ({int((radii > 0).sum())} of {radii.numel()} Gaussians on screen)")
+        if step == a.steps:
+            break
+        loss.backward()
+        opt.step()
+    assert all(np.isfinite(losses)) and losses[-1] < losses[0], losses
+    print(f"loss {losses[0]:.6f} -> {losses[-1]:.6f} in {a.steps} Adam steps over {', '.join(sc.params)}")
+    return losses
+
+
+if __name__ == "__main__":
+    main()

@@ -319,6 +319,35 @@ int mpmhip_render_inputs(int32_t device, void *stream, int32_t n_gaussians, int3
                          const float *extra_rotations, float *means3D, float *means2D, float *opacities, float *scales,
                          float *rotations);
 
+/* ---- gradients through the two steps above (the appearance loop, train_appearance.py: parameters and vertices -> frames ->
+ * binding -> rasteriser -> loss -> backward) --------------------------------------------------------------------------------------
+ * The exact derivative of the forward kernels' expressions with every discrete decision held fixed: the quaternion branch, the
+ * sign inside |a2 . e2| (sign(0) = 0), and the clamps of length() (1e-20) and normalize (1e-12), which pass zero slope where they
+ * bind.  fp32, no atomics: the two reductions walk a CSR segment in ascending index, so two runs give the same bits.
+ *
+ * mpmhip_render_inputs_backward: g_means3D / g_opacities / g_scales / g_rotations are the upstream gradients of the first
+ * n_gaussians rows of mpmhip_render_inputs' outputs (or of mpmhip_bind_gaussians' xyz / scaling / rotation); a NULL one counts
+ * as zero and the raw inputs only it needs may then be NULL too.  d_xyz [n_g*3], d_rotation [n_g*4], d_scaling [n_g*3],
+ * d_opacity [n_g]: written in full, NULL = not wanted.  d_face_center [n_f*3], d_face_orien_mat [n_f*9], d_face_orien_quat
+ * [n_f*4], d_face_scaling [n_f]: all four or none; they need the face -> Gaussian table face_start [n_f+1] (ascending, face_start[0]
+ * = 0, face_start[n_f] = n_g) and face_items [n_g] (the Gaussians of face f, ascending, at face_start[f] .. face_start[f+1]); a face
+ * without Gaussians gets zeros.  The rows of `extra` primitives need no kernel: their gradients are the upstream rows. */
+int mpmhip_render_inputs_backward(int32_t device, void *stream, int32_t n_gaussians, int32_t n_faces, const int32_t *binding,
+                                  const float *xyz_local, const float *rotation_raw, const float *scaling_raw, const float *opacity_raw,
+                                  const float *face_orien_mat, const float *face_orien_quat, const float *face_scaling,
+                                  const float *g_means3D, const float *g_opacities, const float *g_scales, const float *g_rotations,
+                                  float *d_xyz, float *d_rotation, float *d_scaling, float *d_opacity, const int32_t *face_start,
+                                  const int32_t *face_items, float *d_face_center, float *d_face_orien_mat, float *d_face_orien_quat,
+                                  float *d_face_scaling);
+/* mpmhip_face_frames_backward: from the upstream gradients of mpmhip_face_frames' four outputs (a NULL one counts as zero) to
+ * d_verts [n_v*3].  face_orien_mat / face_orien_quat are the forward's own outputs (the quaternion branch is chosen from those
+ * floats); d_corners [n_f*9] is scratch (the gradient of each face's three corners); vert_start [n_v+1] / vert_corners [3*n_f] is
+ * the vertex -> corner table (corner = 3 * face + position, ascending within a vertex); a vertex in no face gets exactly 0. */
+int mpmhip_face_frames_backward(int32_t device, void *stream, const float *verts, const int32_t *faces, int32_t n_faces, int32_t n_verts,
+                                const float *face_orien_mat, const float *face_orien_quat, const float *g_face_center,
+                                const float *g_face_orien_mat, const float *g_face_orien_quat, const float *g_face_scaling,
+                                const int32_t *vert_start, const int32_t *vert_corners, float *d_corners, float *d_verts);
+
 /* MPMWARP.export_particle_cov_to_torch (warp_mpm/mpm_solver.py:543-561) = kernel compute_cov_from_F
  * (warp_mpm/mpm_utils.py:1108-1132): new_cov[6p..] = upper triangle (xx xy xz yy yz zz) of F_trial[p] * sym(particle_cov[6p..])
  * * F_trial[p]^T for p < n (= n_particles - n_vertices).  Stand-alone map on [dev] arrays in the reference's AoS layout. */

@@ -8,12 +8,174 @@
     xyz, rot, scale = frames.get_xyz(binding, _xyz), frames.get_rotation(binding, _rotation), frames.get_scaling(binding, _scaling)
 
 and feed the rasteriser.  No CPU fallback: tensors must live on an MI355X.
+
+Gradients.  With grad mode on, ``set_mesh_by_verts(verts)`` of a ``verts`` that requires grad gives frame tensors that carry a graph
+back to ``verts`` (``verts_orig[t] + verts_offset[t]`` of the appearance loop), and the getters give outputs that carry a graph back to
+whichever of their floating inputs -- the raw parameters, the four frame tensors -- require grad.  The forward is the same launch
+with the same bits; the backward is ``mpmhip_face_frames_backward`` / ``mpmhip_render_inputs_backward`` (csrc/frames_backward.hip):
+the exact derivative of the forward kernels' expressions with every discrete decision held fixed (the quaternion branch, the sign
+inside the absolute value, a clamp that binds passes zero slope), fp32, no atomics, the same bits on every run.  There is no double
+backward.  With grad mode off, or with no floating input requiring grad, nothing changes: the outputs carry no ``grad_fn``.
 """
 from __future__ import annotations
 
 import torch
 
 from . import _lib as L
+
+
+def _csr(keys, n_keys, what):
+    """key -> items table on the device: (start [n_keys + 1] int32, items int32 in ascending item index within a key).  Plumbing for
+    the two reductions of the backward pass, built with torch ops; the bounds of ``keys`` are checked here, once."""
+    k = keys.reshape(-1).long()
+    counts = torch.bincount(k, minlength=n_keys)          # raises on a negative key
+    if counts.numel() != n_keys:
+        raise RuntimeError(f"{what}: index {counts.numel() - 1} out of range [0, {n_keys})")
+    start = torch.zeros(n_keys + 1, dtype=torch.int32, device=keys.device)
+    start[1:] = torch.cumsum(counts, 0)
+    return start, torch.sort(k, stable=True).indices.to(torch.int32)
+
+
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def _call(lib, name, *args):
+    rc = getattr(lib, name)(*args)
+    if rc != L.OK:
+        raise L.MPMHipError(rc, f"{name} failed")
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _launch_face_frames(lib, faces, v):
+    n_f = faces.shape[0]
+    dev = v.device
+    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    center, mat, quat, scale = new(n_f, 3), new(n_f, 3, 3), new(n_f, 4), new(n_f, 1)
+    _call(lib, "mpmhip_face_frames", dev.index or 0, torch.cuda.current_stream(dev).cuda_stream, v.data_ptr(), faces.data_ptr(), n_f,
+          center.data_ptr(), mat.data_ptr(), quat.data_ptr(), scale.data_ptr())
+    return center, mat, quat, scale
+
+
+def _launch_bind(lib, render, means2D, binding, frame, params, extra):
+    """One launch of the binding: mpmhip_render_inputs (``render``: all four parameters, n + m rows with the ``extra`` tensors behind,
+    means2D cleared through its pointer) or mpmhip_bind_gaussians (any of xyz / rotation / scaling).  -> (means3D / xyz, rotations,
+    scales, opacities), None where a parameter was not given."""
+    dev = binding.device
+    n, m = binding.numel(), (0 if extra[0] is None else extra[0].shape[0])
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    o_xyz, o_rot, o_scl, o_opa = [None if t is None else torch.empty(n + m, w, dtype=torch.float32, device=dev)
+                                  for t, w in zip(params, (3, 4, 3, 1))]
+    xyz, rot, scl, opa = params
+    if render:
+        _call(lib, "mpmhip_render_inputs", dev.index or 0, stream, n, m, binding.data_ptr(), xyz.data_ptr(), rot.data_ptr(),
+              scl.data_ptr(), opa.data_ptr(), *[t.data_ptr() for t in frame], *[_ptr(t) for t in extra], o_xyz.data_ptr(), means2D,
+              o_opa.data_ptr(), o_scl.data_ptr(), o_rot.data_ptr())
+    else:
+        _call(lib, "mpmhip_bind_gaussians", dev.index or 0, stream, n, binding.data_ptr(), _ptr(xyz), _ptr(rot), _ptr(scl),
+              *[t.data_ptr() for t in frame], _ptr(o_xyz), _ptr(o_rot), _ptr(o_scl))
+    return o_xyz, o_rot, o_scl, o_opa
+
+
+class _FaceFrames(torch.autograd.Function):
+    """verts -> (face_center, face_orien_mat, face_orien_quat, face_scaling): the forward launch of set_mesh_by_verts with a backward."""
+
+    @staticmethod
+    def forward(ctx, verts, lib, faces, vtable):
+        out = _launch_face_frames(lib, faces, verts)
+        ctx.lib, ctx.faces, ctx.vtable = lib, faces, vtable
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(verts, out[1], out[2])
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_center, g_mat, g_quat, g_scale):
+        verts, mat, quat = ctx.saved_tensors
+        faces = ctx.faces
+        n_f, n_v, dev = faces.shape[0], verts.shape[0], verts.device
+        start, corners = ctx.vtable.get(faces, n_v)
+        g = [None if t is None else t.to(torch.float32).contiguous() for t in (g_center, g_mat, g_quat, g_scale)]
+        d_corners = torch.empty(n_f, 3, 3, dtype=torch.float32, device=dev)
+        d_verts = torch.empty_like(verts)
+        _call(ctx.lib, "mpmhip_face_frames_backward", dev.index or 0, torch.cuda.current_stream(dev).cuda_stream, verts.data_ptr(),
+              faces.data_ptr(), n_f, n_v, mat.data_ptr(), quat.data_ptr(), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(g[3]),
+              start.data_ptr(), corners.data_ptr(), d_corners.data_ptr(), d_verts.data_ptr())
+        return d_verts, None, None, None
+
+
+class _Bind(torch.autograd.Function):
+    """The binding launch (mpmhip_render_inputs with ``render``, else mpmhip_bind_gaussians) with a backward.  Outputs: (means3D / xyz,
+    rotations, scales, opacities), None where an input was not given; with ``render`` they have n + m rows, the ``extra`` tensors behind.
+    ``table`` is the caller's face -> Gaussian table (_GaussianTable); ``key`` is the caller's binding tensor, which the table is
+    keyed on; means2D is written through its pointer and is no part of the graph."""
+
+    @staticmethod
+    def forward(ctx, lib, table, key, render, means2D, binding, center, mat, quat, fscale, xyz, rot, scl, opa, x_xyz, x_opa, x_scl, x_rot):
+        out = _launch_bind(lib, render, means2D, binding, (center, mat, quat, fscale), (xyz, rot, scl, opa), (x_xyz, x_opa, x_scl, x_rot))
+        n = binding.numel()
+        ctx.lib, ctx.table, ctx.n, ctx.n_f = lib, table, n, fscale.shape[0]
+        ctx.key = (key, key.data_ptr(), key._version)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(binding, mat, quat, fscale, xyz, rot, scl, opa)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_xyz, g_rot, g_scl, g_opa):
+        binding, mat, quat, fscale, xyz, rot, scl, opa = ctx.saved_tensors
+        n, n_f, dev = ctx.n, ctx.n_f, binding.device
+        need = ctx.needs_input_grad
+        g = [None if t is None else t.to(torch.float32).contiguous() for t in (g_xyz, g_rot, g_scl, g_opa)]
+        out = lambda want, t: torch.empty_like(t) if want and t is not None else None
+        d_xyz, d_rot, d_scl, d_opa = out(need[10], xyz), out(need[11], rot), out(need[12], scl), out(need[13], opa)
+        d_face = [None] * 4
+        start = items = None
+        if any(need[6:10]):
+            start, items = ctx.table.get(ctx.key, binding, n_f)
+            d_face = [torch.empty(n_f, w, dtype=torch.float32, device=dev) for w in (3, 9, 4, 1)]
+        _call(ctx.lib, "mpmhip_render_inputs_backward", dev.index or 0, torch.cuda.current_stream(dev).cuda_stream, n, n_f,
+              binding.data_ptr(), _ptr(xyz), _ptr(rot), _ptr(scl), _ptr(opa), mat.data_ptr(), quat.data_ptr(), fscale.data_ptr(),
+              _ptr(g[0]), _ptr(g[3]), _ptr(g[2]), _ptr(g[1]), _ptr(d_xyz), _ptr(d_rot), _ptr(d_scl), _ptr(d_opa), _ptr(start), _ptr(items),
+              *[_ptr(t) for t in d_face])
+        d_center, d_mat, d_quat, d_fscale = [t if want else None for t, want in zip(d_face, need[6:10])]
+        if d_mat is not None:
+            d_mat = d_mat.view(n_f, 3, 3)
+        # the rows behind the bound Gaussians are the `extra` tensors copied: their gradients are the upstream rows
+        tail = lambda want, t: t[n:] if want and t is not None else None
+        return (None, None, None, None, None, None, d_center, d_mat, d_quat, d_fscale, d_xyz, d_rot, d_scl, d_opa,
+                tail(need[14], g[0]), tail(need[15], g[3]), tail(need[16], g[2]), tail(need[17], g[1]))
+
+
+class _GaussianTable:
+    """The face -> Gaussian table of the backward pass, built at the first backward and kept while the binding tensor it was built
+    from is the same storage at the same version: densification (a new tensor) or an in-place edit rebuilds it."""
+
+    def __init__(self):
+        self._t = None
+
+    def get(self, key, binding, n_f):
+        tensor, ptr, version = key
+        t = self._t
+        if t is None or t[0] is not tensor or t[1:4] != (ptr, version, n_f):
+            self._t = t = (tensor, ptr, version, n_f) + _csr(binding, n_f, "binding")   # holds `tensor`: its address is not reused
+        return t[4], t[5]
+
+
+class _VertexTable:
+    """The vertex -> corner table (corner = 3 * face + position) of the backward pass: the faces are fixed, so it is built once per
+    vertex count."""
+
+    def __init__(self):
+        self._t = None
+
+    def get(self, faces, n_v):
+        if self._t is None or self._t[0] != n_v:
+            self._t = (n_v,) + _csr(faces, n_v, "faces")
+        return self._t[1:]
 
 
 def _chk(t, dtype, name, shape_last=None):
@@ -28,50 +190,35 @@ class MeshFrames:
     def __init__(self, faces: torch.Tensor):
         self.faces = _chk(faces.to(torch.int32).contiguous(), torch.int32, "faces", 3)
         self._lib = L.load()
+        self._vtable, self._gtable = _VertexTable(), _GaussianTable()
         self.verts = None
         self.face_center = self.face_orien_mat = self.face_orien_quat = self.face_scaling = None
-
-    def _call(self, name, *args):
-        rc = getattr(self._lib, name)(*args)
-        if rc != L.OK:
-            raise L.MPMHipError(rc, f"{name} failed")
 
     # mesh_gaussian_model.py:137-146
     def set_mesh_by_verts(self, verts: torch.Tensor):
         v = _chk(verts, torch.float32, "verts", 3)
         if v.device != self.faces.device:
             raise RuntimeError("verts and faces must be on the same device")
-        n_f = self.faces.shape[0]
-        dev = v.device
-        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         self.verts = v
-        self.face_center, self.face_orien_mat = new(n_f, 3), new(n_f, 3, 3)
-        self.face_orien_quat, self.face_scaling = new(n_f, 4), new(n_f, 1)
-        self._call("mpmhip_face_frames", dev.index or 0, torch.cuda.current_stream(dev).cuda_stream, v.data_ptr(),
-                   self.faces.data_ptr(), n_f, self.face_center.data_ptr(), self.face_orien_mat.data_ptr(),
-                   self.face_orien_quat.data_ptr(), self.face_scaling.data_ptr())
+        if _wants_grad(v):
+            out = _FaceFrames.apply(v, self._lib, self.faces, self._vtable)
+        else:
+            out = _launch_face_frames(self._lib, self.faces, v)
+        self.face_center, self.face_orien_mat, self.face_orien_quat, self.face_scaling = out
 
     def _bind(self, binding, xyz_local=None, rotation=None, scaling=None):
         if self.face_center is None:
             raise RuntimeError("call set_mesh_by_verts first")
         b = _chk(binding.to(torch.int32).contiguous(), torch.int32, "binding")
-        n = b.numel()
-        dev = b.device
-        out = [None, None, None]
-        ptr = lambda t: None if t is None else t.data_ptr()
-        if xyz_local is not None:
-            _chk(xyz_local, torch.float32, "_xyz", 3)
-            out[0] = torch.empty(n, 3, dtype=torch.float32, device=dev)
-        if rotation is not None:
-            _chk(rotation, torch.float32, "_rotation", 4)
-            out[1] = torch.empty(n, 4, dtype=torch.float32, device=dev)
-        if scaling is not None:
-            _chk(scaling, torch.float32, "_scaling", 3)
-            out[2] = torch.empty(n, 3, dtype=torch.float32, device=dev)
-        self._call("mpmhip_bind_gaussians", dev.index or 0, torch.cuda.current_stream(dev).cuda_stream, n, b.data_ptr(),
-                   ptr(xyz_local), ptr(rotation), ptr(scaling), self.face_center.data_ptr(), self.face_orien_mat.data_ptr(),
-                   self.face_orien_quat.data_ptr(), self.face_scaling.data_ptr(), ptr(out[0]), ptr(out[1]), ptr(out[2]))
-        return out
+        for t, name, w in ((xyz_local, "_xyz", 3), (rotation, "_rotation", 4), (scaling, "_scaling", 3)):
+            if t is not None:
+                _chk(t, torch.float32, name, w)
+        fr = (self.face_center, self.face_orien_mat, self.face_orien_quat, self.face_scaling)
+        if _wants_grad(xyz_local, rotation, scaling, *fr):
+            out = _Bind.apply(self._lib, self._gtable, binding, False, None, b, *fr, xyz_local, rotation, scaling, None, None, None, None, None)
+        else:
+            out = _launch_bind(self._lib, False, None, b, fr, (xyz_local, rotation, scaling, None), (None,) * 4)
+        return list(out[:3])
 
     # gaussian_model.py:141-151 / :124-138 / :112-122 (binding is not None branch)
     def get_xyz(self, binding, xyz_local):

@@ -11,13 +11,21 @@ primitives concatenated behind, :84-91) in one launch (``mpmhip_render_inputs``)
     frames = MeshFrames(faces);  frames.set_mesh_by_verts(sim2wld(state.particle_x[n_e + n_t:]))
     args = gaussians.render_inputs(frames, override_color=colors, extra=(xyz, colors, opacity, scales, rotations))
     rasterizer(**args)          # keys: means3D means2D shs colors_precomp opacities scales rotations cov3Ds_precomp
+
+Training (train_appearance.py).  With grad mode on, ``means3D``, ``opacities``, ``scales`` and ``rotations`` carry a graph back to
+whichever of ``_xyz``, ``_rotation``, ``_scaling``, ``_opacity`` (``nn.Parameter`` or not), the four frame tensors and the ``extra``
+tensors require grad; the forward is the same launch with the same bits, the backward is ``mpmhip_render_inputs_backward``
+(csrc/frames_backward.hip), and the ``extra`` rows get the upstream rows back.  ``colors_precomp`` / ``shs`` are torch's own ``cat``.
+``means2D`` stays a fresh zero tensor outside the graph: a trainer that wants ``viewspace_points.grad`` for densification calls
+``args["means2D"].requires_grad_(True)`` before the render call, as the reference does with its ``screenspace_points``.  With grad mode
+off, or with nothing requiring grad, nothing changes and the outputs carry no ``grad_fn``.
 """
 from __future__ import annotations
 
 import torch
 
 from . import _lib as L
-from .mesh_frames import MeshFrames, _chk
+from .mesh_frames import MeshFrames, _Bind, _GaussianTable, _chk, _launch_bind, _wants_grad
 
 
 class BoundGaussians:
@@ -34,6 +42,7 @@ class BoundGaussians:
         if not (self._xyz.shape[0] == self._rotation.shape[0] == self._scaling.shape[0] == self._opacity.shape[0] == n):
             raise RuntimeError("BoundGaussians: parameter tensors must have one row per binding entry")
         self._lib = L.load()
+        self._gtable = _GaussianTable()
 
     @property
     def get_features(self):  # gaussian_model.py:153-157
@@ -52,17 +61,14 @@ class BoundGaussians:
                 raise RuntimeError("extra primitives carry precomputed colours: pass override_color for the bound Gaussians too")
             ex = [_chk(t.contiguous(), torch.float32, f"extra[{i}]", w) for i, (t, w) in enumerate(zip(extra, (3, 3, 1, 3, 4)))]
             m = ex[0].shape[0]
-        new = lambda w: torch.empty(n + m, w, dtype=torch.float32, device=dev)
-        means3D, means2D, opac, scales, rots = new(3), new(3), new(1), new(3), new(4)
-        p = lambda t: None if t is None else t.data_ptr()
-        rc = self._lib.mpmhip_render_inputs(dev.index or 0, torch.cuda.current_stream(dev).cuda_stream, n, m, self.binding.data_ptr(),
-                                            self._xyz.data_ptr(), self._rotation.data_ptr(), self._scaling.data_ptr(),
-                                            self._opacity.data_ptr(), frames.face_center.data_ptr(), frames.face_orien_mat.data_ptr(),
-                                            frames.face_orien_quat.data_ptr(), frames.face_scaling.data_ptr(), p(ex[0]), p(ex[2]),
-                                            p(ex[3]), p(ex[4]), means3D.data_ptr(), means2D.data_ptr(), opac.data_ptr(),
-                                            scales.data_ptr(), rots.data_ptr())
-        if rc != L.OK:
-            raise L.MPMHipError(rc, "mpmhip_render_inputs failed")
+        fr = (frames.face_center, frames.face_orien_mat, frames.face_orien_quat, frames.face_scaling)
+        params, tail = (self._xyz, self._rotation, self._scaling, self._opacity), (ex[0], ex[2], ex[3], ex[4])
+        means2D = torch.empty(n + m, 3, dtype=torch.float32, device=dev)     # cleared by the same launch; a fresh leaf, outside the graph
+        if _wants_grad(*params, *fr, *tail):
+            out = _Bind.apply(self._lib, self._gtable, self.binding, True, means2D.data_ptr(), self.binding, *fr, *params, *tail)
+        else:
+            out = _launch_bind(self._lib, True, means2D.data_ptr(), self.binding, fr, params, tail)
+        means3D, rots, scales, opac = out
         shs = colors = None
         if override_color is None:
             shs = self.get_features                      # SH -> RGB in the rasteriser (:81)
