@@ -9,10 +9,11 @@
 
 #include <cstdint>
 
-#include "../../include/mpmhip.h"
+#include "entry.hpp"
 
 namespace {
 
+using namespace entry;
 constexpr int TPB = 256;
 
 struct F3 { float x, y, z; };
@@ -170,8 +171,6 @@ __global__ void k_cov_from_F(const float *F_trial, const float *cov0, int n, flo
     for (int c = r; c < 3; ++c) o[k++] = T[r][0] * F[c][0] + T[r][1] * F[c][1] + T[r][2] * F[c][2];
 }
 
-int check(hipError_t e) { return e == hipSuccess ? MPMHIP_OK : MPMHIP_ERR_HIP; }
-
 }  // namespace
 
 extern "C" {
@@ -179,25 +178,22 @@ extern "C" {
 int mpmhip_cov_from_F(int32_t device, void *stream, const float *particle_F_trial, const float *particle_cov, int32_t n,
                       float *new_cov) {
   if (n < 0 || (n > 0 && (!particle_F_trial || !particle_cov || !new_cov))) return MPMHIP_ERR_INVALID;
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0 || device < 0 || device >= n_dev) return MPMHIP_ERR_NO_DEVICE;
+  if (int rc = device_in_range(device)) return rc;
   if (n == 0) return MPMHIP_OK;
-  if (int rc = check(hipSetDevice(device))) return rc;
-  hipLaunchKernelGGL(k_cov_from_F, (unsigned)((n + TPB - 1) / TPB), TPB, 0, (hipStream_t)stream, particle_F_trial, particle_cov, n,
+  ENTRY_CHECK(hipSetDevice(device));
+  hipLaunchKernelGGL(k_cov_from_F, blocks(n, TPB), TPB, 0, (hipStream_t)stream, particle_F_trial, particle_cov, n,
                      new_cov);
   return check(hipGetLastError());
 }
-
 
 int mpmhip_face_frames(int32_t device, void *stream, const float *verts, const int32_t *faces, int32_t n_faces,
                        float *face_center, float *face_orien_mat, float *face_orien_quat, float *face_scaling) {
   if (n_faces < 0 || (n_faces > 0 && (!verts || !faces || !face_center || !face_orien_mat || !face_orien_quat || !face_scaling)))
     return MPMHIP_ERR_INVALID;
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0 || device < 0 || device >= n_dev) return MPMHIP_ERR_NO_DEVICE;
+  if (int rc = device_in_range(device)) return rc;
   if (n_faces == 0) return MPMHIP_OK;
-  if (int rc = check(hipSetDevice(device))) return rc;
-  hipLaunchKernelGGL(k_face_frames, (unsigned)((n_faces + TPB - 1) / TPB), TPB, 0, (hipStream_t)stream, verts, faces, n_faces,
+  ENTRY_CHECK(hipSetDevice(device));
+  hipLaunchKernelGGL(k_face_frames, blocks(n_faces, TPB), TPB, 0, (hipStream_t)stream, verts, faces, n_faces,
                      face_center, face_orien_mat, face_orien_quat, face_scaling);
   return check(hipGetLastError());
 }
@@ -210,11 +206,10 @@ int mpmhip_bind_gaussians(int32_t device, void *stream, int32_t n_gaussians, con
   if (n_gaussians > 0 && (!binding || !face_scaling || (xyz && (!xyz_local || !face_center || !face_orien_mat)) ||
                           (rotation && (!rotation_raw || !face_orien_quat)) || (scaling && !scaling_raw)))
     return MPMHIP_ERR_INVALID;
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0 || device < 0 || device >= n_dev) return MPMHIP_ERR_NO_DEVICE;
+  if (int rc = device_in_range(device)) return rc;
   if (n_gaussians == 0) return MPMHIP_OK;
-  if (int rc = check(hipSetDevice(device))) return rc;
-  hipLaunchKernelGGL(k_bind_gaussians, (unsigned)((n_gaussians + TPB - 1) / TPB), TPB, 0, (hipStream_t)stream, n_gaussians,
+  ENTRY_CHECK(hipSetDevice(device));
+  hipLaunchKernelGGL(k_bind_gaussians, blocks(n_gaussians, TPB), TPB, 0, (hipStream_t)stream, n_gaussians,
                      binding, xyz_local, rotation_raw, scaling_raw, face_center, face_orien_mat, face_orien_quat,
                      face_scaling, xyz, rotation, scaling);
   return check(hipGetLastError());
@@ -232,11 +227,10 @@ int mpmhip_render_inputs(int32_t device, void *stream, int32_t n_gaussians, int3
                           !face_orien_quat || !face_scaling))
     return MPMHIP_ERR_INVALID;
   if (n_extra > 0 && (!extra_xyz || !extra_opacity || !extra_scales || !extra_rotations)) return MPMHIP_ERR_INVALID;
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0 || device < 0 || device >= n_dev) return MPMHIP_ERR_NO_DEVICE;
+  if (int rc = device_in_range(device)) return rc;
   if (n_gaussians + n_extra == 0) return MPMHIP_OK;
-  if (int rc = check(hipSetDevice(device))) return rc;
-  hipLaunchKernelGGL(k_render_inputs, (unsigned)((n_gaussians + n_extra + TPB - 1) / TPB), TPB, 0, (hipStream_t)stream, n_gaussians,
+  ENTRY_CHECK(hipSetDevice(device));
+  hipLaunchKernelGGL(k_render_inputs, blocks(n_gaussians + n_extra, TPB), TPB, 0, (hipStream_t)stream, n_gaussians,
                      n_extra, binding, xyz_local, rotation_raw, scaling_raw, opacity_raw, face_center, face_orien_mat, face_orien_quat,
                      face_scaling, extra_xyz, extra_opacity, extra_scales, extra_rotations, means3D, means2D, opacities, scales,
                      rotations);

@@ -10,11 +10,12 @@
 
 #include <cstdint>
 
-#include "../../include/mpmhip.h"
+#include "entry.hpp"
 #include "frames_grad_math.hpp"
 
 namespace {
 
+using namespace entry;
 constexpr int TPB = 256;
 
 __global__ void k_gaussian_backward(int n_g, const int32_t *binding, const float *rot_raw, const float *scaling_raw,
@@ -50,9 +51,6 @@ __global__ void k_vertex_gather(int n_v, const int32_t *start, const int32_t *co
   fgrad::vertex_gather(v, start, corners, d_corner, d_verts);
 }
 
-int check(hipError_t e) { return e == hipSuccess ? MPMHIP_OK : MPMHIP_ERR_HIP; }
-unsigned blocks(int n) { return (unsigned)((n + TPB - 1) / TPB); }
-
 }  // namespace
 
 extern "C" {
@@ -77,22 +75,21 @@ int mpmhip_render_inputs_backward(int32_t device, void *stream, int32_t n_gaussi
     if (g_scales && !scaling_raw) return MPMHIP_ERR_INVALID;
     if (g_opacities && d_opacity && !opacity_raw) return MPMHIP_ERR_INVALID;
   }
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0 || device < 0 || device >= n_dev) return MPMHIP_ERR_NO_DEVICE;
+  if (int rc = device_in_range(device)) return rc;
   const bool run1 = params && n_gaussians > 0, run2 = all_face && n_faces > 0;
   if (!run1 && !run2) return MPMHIP_OK;
-  if (int rc = check(hipSetDevice(device))) return rc;
+  ENTRY_CHECK(hipSetDevice(device));
   if (run1) {
-    hipLaunchKernelGGL(k_gaussian_backward, blocks(n_gaussians), TPB, 0, (hipStream_t)stream, n_gaussians, binding, rotation_raw,
+    hipLaunchKernelGGL(k_gaussian_backward, blocks(n_gaussians, TPB), TPB, 0, (hipStream_t)stream, n_gaussians, binding, rotation_raw,
                        scaling_raw, opacity_raw, face_orien_mat, face_orien_quat, face_scaling, g_means3D, g_rotations, g_scales,
                        g_opacities, d_xyz, d_rotation, d_scaling, d_opacity);
-    if (int rc = check(hipGetLastError())) return rc;
+    ENTRY_CHECK(hipGetLastError());
   }
   if (run2) {
-    hipLaunchKernelGGL(k_face_accumulate, blocks(n_faces), TPB, 0, (hipStream_t)stream, n_faces, face_start, face_items, xyz_local,
+    hipLaunchKernelGGL(k_face_accumulate, blocks(n_faces, TPB), TPB, 0, (hipStream_t)stream, n_faces, face_start, face_items, xyz_local,
                        rotation_raw, scaling_raw, face_orien_mat, face_orien_quat, face_scaling, g_means3D, g_rotations, g_scales,
                        d_face_center, d_face_orien_mat, d_face_orien_quat, d_face_scaling);
-    if (int rc = check(hipGetLastError())) return rc;
+    ENTRY_CHECK(hipGetLastError());
   }
   return MPMHIP_OK;
 }
@@ -104,16 +101,15 @@ int mpmhip_face_frames_backward(int32_t device, void *stream, const float *verts
   if (n_faces < 0 || n_verts < 0) return MPMHIP_ERR_INVALID;
   if (n_faces > 0 && (!verts || !faces || !face_orien_mat || !face_orien_quat || !d_corners || !vert_corners)) return MPMHIP_ERR_INVALID;
   if (n_verts > 0 && (!vert_start || !d_verts)) return MPMHIP_ERR_INVALID;
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0 || device < 0 || device >= n_dev) return MPMHIP_ERR_NO_DEVICE;
+  if (int rc = device_in_range(device)) return rc;
   if (n_verts == 0) return MPMHIP_OK;
-  if (int rc = check(hipSetDevice(device))) return rc;
+  ENTRY_CHECK(hipSetDevice(device));
   if (n_faces > 0) {
-    hipLaunchKernelGGL(k_face_frames_backward, blocks(n_faces), TPB, 0, (hipStream_t)stream, n_faces, verts, faces, face_orien_mat,
+    hipLaunchKernelGGL(k_face_frames_backward, blocks(n_faces, TPB), TPB, 0, (hipStream_t)stream, n_faces, verts, faces, face_orien_mat,
                        face_orien_quat, g_face_center, g_face_orien_mat, g_face_orien_quat, g_face_scaling, d_corners);
-    if (int rc = check(hipGetLastError())) return rc;
+    ENTRY_CHECK(hipGetLastError());
   }
-  hipLaunchKernelGGL(k_vertex_gather, blocks(n_verts), TPB, 0, (hipStream_t)stream, n_verts, vert_start, vert_corners, d_corners, d_verts);
+  hipLaunchKernelGGL(k_vertex_gather, blocks(n_verts, TPB), TPB, 0, (hipStream_t)stream, n_verts, vert_start, vert_corners, d_corners, d_verts);
   return check(hipGetLastError());
 }
 

@@ -10,11 +10,12 @@
 
 #include <cstdint>
 
-#include "../../include/mpmhip.h"
+#include "entry.hpp"
 #include "geo_math.hpp"
 
 namespace {
 
+using namespace entry;
 using geo::P3;
 
 constexpr int TPB = 256;
@@ -186,16 +187,6 @@ __global__ void k_geo_final(const double *scratch, int n1, int n2, double *out) 
   out[3] = f.recall;
 }
 
-int check(hipError_t e) { return e == hipSuccess ? MPMHIP_OK : MPMHIP_ERR_HIP; }
-
-int select_device(int32_t device) {
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0 || device < 0 || device >= n_dev) return MPMHIP_ERR_NO_DEVICE;
-  return check(hipSetDevice(device));
-}
-
-unsigned blocks(int64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
-
 }  // namespace
 
 extern "C" {
@@ -203,7 +194,7 @@ extern "C" {
 int mpmhip_face_areas(int32_t device, void *stream, const float *verts, const int32_t *faces, int32_t n_faces, float *area) {
   if (n_faces <= 0 || !verts || !faces || !area) return MPMHIP_ERR_INVALID;
   if (int rc = select_device(device)) return rc;
-  hipLaunchKernelGGL(k_face_areas, blocks(n_faces), TPB, 0, (hipStream_t)stream, verts, faces, n_faces, area);
+  hipLaunchKernelGGL(k_face_areas, blocks(n_faces, TPB), TPB, 0, (hipStream_t)stream, verts, faces, n_faces, area);
   return check(hipGetLastError());
 }
 
@@ -212,7 +203,7 @@ int mpmhip_mesh_sample(int32_t device, void *stream, const float *verts, const i
                        int32_t *face_index) {
   if (n_faces <= 0 || n_samples <= 0 || !verts || !faces || !area_cdf || !uniforms || !points) return MPMHIP_ERR_INVALID;
   if (int rc = select_device(device)) return rc;
-  hipLaunchKernelGGL(k_mesh_sample, blocks(n_samples), TPB, 0, (hipStream_t)stream, verts, faces, n_faces, area_cdf, uniforms,
+  hipLaunchKernelGGL(k_mesh_sample, blocks(n_samples, TPB), TPB, 0, (hipStream_t)stream, verts, faces, n_faces, area_cdf, uniforms,
                      n_samples, points, face_index);
   return check(hipGetLastError());
 }
@@ -234,10 +225,10 @@ int mpmhip_nn_dist2(int32_t device, void *stream, const float *src, int32_t n_sr
   const int slice_len = (int)(((int64_t)n_dst + slices - 1) / slices);
   slices = (n_dst + slice_len - 1) / slice_len;  // no empty slice at the end
   hipStream_t s = (hipStream_t)stream;
-  if (int rc = check(hipMemsetAsync(best_scratch, 0xff, (size_t)n_src * sizeof(uint64_t), s))) return rc;
+  ENTRY_CHECK(hipMemsetAsync(best_scratch, 0xff, (size_t)n_src * sizeof(uint64_t), s));
   hipLaunchKernelGGL(k_nn_d2, dim3((unsigned)tiles, (unsigned)slices), TPB, 0, s, src, n_src, dst, n_dst, slice_len,
                      (unsigned long long *)best_scratch);
-  hipLaunchKernelGGL(k_nn_unpack, blocks(n_src), TPB, 0, s, (const unsigned long long *)best_scratch, n_src, dist2, index);
+  hipLaunchKernelGGL(k_nn_unpack, blocks(n_src, TPB), TPB, 0, s, (const unsigned long long *)best_scratch, n_src, dist2, index);
   return check(hipGetLastError());
 }
 

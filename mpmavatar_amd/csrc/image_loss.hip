@@ -16,11 +16,12 @@
 
 #include <cstdint>
 
-#include "../../include/mpmhip.h"
+#include "entry.hpp"
 #include "image_loss_math.hpp"
 
 namespace {
 
+using namespace entry;
 using imgloss::HALO;
 using imgloss::RAD;
 using imgloss::TILE;
@@ -148,14 +149,6 @@ __global__ __launch_bounds__(TPB) void k_image_loss_backward(const float *__rest
   const float c_mu = imgloss::taps(&hc[0][at], TILE), c_s1 = imgloss::taps(&hc[1][at], TILE), c_s12 = imgloss::taps(&hc[2][at], TILE);
   const size_t o = (size_t)tp.plane * hw + (size_t)gy * W + gx;
   d_img[o] = imgloss::pixel_grad(img[o], gt[o], c_mu, c_s1, c_s12, g_l1[tp.plane], g_mse[tp.plane], g_ssim[tp.plane], inv_n);
-}
-
-int check(hipError_t e) { return e == hipSuccess ? MPMHIP_OK : MPMHIP_ERR_HIP; }
-
-int select_device(int32_t device) {
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0 || device < 0 || device >= n_dev) return MPMHIP_ERR_NO_DEVICE;
-  return check(hipSetDevice(device));
 }
 
 bool sizes_ok(int32_t planes, int32_t H, int32_t W) {

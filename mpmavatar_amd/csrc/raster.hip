@@ -23,6 +23,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
+#include "entry.hpp"
 #include "raster_state.hpp"
 
 namespace {
@@ -184,7 +185,7 @@ unsigned bits_for(int tiles) {  // ceil(log2(tiles))
 
 int reserve_grad(mpmhip_raster *r, size_t pixels, size_t total) {
   if (pixels > r->cap_pix) {
-    RS_CHECK(hipStreamSynchronize(r->stream));
+    ENTRY_CHECK(hipStreamSynchronize(r->stream));
     const size_t cap = grown(r->cap_pix, pixels);
     r->cap_pix = 0;
     if (int rc = regrow(r->pix_T, cap)) return rc;
@@ -192,7 +193,7 @@ int reserve_grad(mpmhip_raster *r, size_t pixels, size_t total) {
     r->cap_pix = cap;
   }
   if (total > r->cap_inv) {
-    RS_CHECK(hipStreamSynchronize(r->stream));
+    ENTRY_CHECK(hipStreamSynchronize(r->stream));
     const size_t cap = grown(r->cap_inv, total);
     r->cap_inv = 0;
     if (int rc = regrow(r->inv, cap)) return rc;
@@ -213,9 +214,7 @@ extern "C" {
 int mpmhip_raster_create(int32_t device, void *stream, mpmhip_raster **out) {
   if (!out) return MPMHIP_ERR_INVALID;
   *out = nullptr;
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0 || device < 0 || device >= n_dev) return MPMHIP_ERR_NO_DEVICE;
-  RS_CHECK(hipSetDevice(device));
+  if (int rc = select_device(device)) return rc;
   mpmhip_raster *r = new (std::nothrow) mpmhip_raster();
   if (!r) return MPMHIP_ERR_HIP;
   r->device = device;
@@ -273,7 +272,7 @@ int mpmhip_raster_save(mpmhip_raster *r, void *dst, int64_t bytes) {
   const size_t n = (size_t)r->grad_n, e = (size_t)r->grad_entries;
   const SavedLayout l = saved_layout(n, (size_t)r->grad_tiles, r->grad_pixels, e);
   if (bytes != (int64_t)l.bytes) return MPMHIP_ERR_INVALID;
-  RS_CHECK(hipSetDevice(r->device));
+  ENTRY_CHECK(hipSetDevice(r->device));
   char *d = (char *)dst;
   auto copy = [&](size_t at, const void *src, size_t size) {
     return size == 0 ? MPMHIP_OK : check(hipMemcpyAsync(d + at, src, size, hipMemcpyDeviceToDevice, r->stream));
@@ -299,24 +298,16 @@ int forward_impl(mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, c
                  int32_t n_sh_coeffs, const float *colors_precomp, const float *opacities, const float *scales,
                  const float *rotations, const float *cov3D_precomp, float *out_color, float *out_alpha, int32_t *radii,
                  const bool grad) {
-  if (!r || !s || n < 0 || s->image_height <= 0 || s->image_width <= 0 || !out_color || !out_alpha) return MPMHIP_ERR_INVALID;
-  if (!s->viewmatrix || !s->projmatrix || !s->campos) return MPMHIP_ERR_INVALID;
-  if (n > 0) {
-    if (!means3D || !opacities || !radii) return MPMHIP_ERR_INVALID;
-    if ((shs != nullptr) == (colors_precomp != nullptr)) return MPMHIP_ERR_INVALID;
-    const bool sr = scales && rotations;
-    if ((scales != nullptr) != (rotations != nullptr) || sr == (cov3D_precomp != nullptr)) return MPMHIP_ERR_INVALID;
-    if (shs && (s->sh_degree < 0 || s->sh_degree > 3 || n_sh_coeffs < (s->sh_degree + 1) * (s->sh_degree + 1))) return MPMHIP_ERR_INVALID;
-  }
-  const int W = s->image_width, H = s->image_height;
-  const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-  if ((int64_t)gx * gy > INT32_MAX || gy > 65535) return MPMHIP_ERR_LIMIT;
-  const int tiles = gx * gy;
-  RS_CHECK(hipSetDevice(r->device));
+  if (!out_color || !out_alpha || (n > 0 && !radii)) return MPMHIP_ERR_INVALID;
+  const Inputs in{means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, n_sh_coeffs};
+  int gx = 0, gy = 0;
+  if (int rc = validate_frame(r, s, n, in, &gx, &gy)) return rc;
+  const int W = s->image_width, H = s->image_height, tiles = gx * gy;
+  ENTRY_CHECK(hipSetDevice(r->device));
   hipStream_t st = r->stream;
   if (int rc = reserve_tiles(r, tiles)) return rc;
   if (int rc = reserve_gaussians(r, n > 0 ? n : 1)) return rc;
-  RS_CHECK(hipMemsetAsync(r->ranges, 0, (size_t)tiles * sizeof(uint2), st));
+  ENTRY_CHECK(hipMemsetAsync(r->ranges, 0, (size_t)tiles * sizeof(uint2), st));
   r->last_n = n; r->last_tiles = tiles; r->last_entries = 0;
   r->grad_frame = false;
 
@@ -324,16 +315,16 @@ int forward_impl(mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, c
   if (int rc = mark(r, 0)) return rc;
   if (n > 0) {
     Camera cam{W, H, gx, gy, s->tanfovx, s->tanfovy, s->scale_modifier, s->sh_degree, s->viewmatrix, s->projmatrix, s->campos};
-    hipLaunchKernelGGL(k_raster_preprocess, blocks((int64_t)n + 1), TPB, 0, st, n, cam, means3D, shs, n_sh_coeffs, colors_precomp,
+    hipLaunchKernelGGL(k_raster_preprocess, blocks((int64_t)n + 1, TPB), TPB, 0, st, n, cam, means3D, shs, n_sh_coeffs, colors_precomp,
                        opacities, scales, rotations, cov3D_precomp, r->rec0, r->rec1, r->colour, r->rect, r->touched, radii);
-    RS_CHECK(hipGetLastError());
+    ENTRY_CHECK(hipGetLastError());
     if (int rc = mark(r, 1)) return rc;
     size_t tmp = 0;
-    RS_CHECK(rocprim::exclusive_scan(nullptr, tmp, r->touched, r->offsets, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
+    ENTRY_CHECK(rocprim::exclusive_scan(nullptr, tmp, r->touched, r->offsets, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
     if (int rc = reserve_tmp(r, r->scan_tmp, r->scan_tmp_bytes, tmp)) return rc;
-    RS_CHECK(rocprim::exclusive_scan(r->scan_tmp, tmp, r->touched, r->offsets, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
-    RS_CHECK(hipMemcpyAsync(r->h_total, r->offsets + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    RS_CHECK(hipStreamSynchronize(st));  // the one synchronisation of a frame
+    ENTRY_CHECK(rocprim::exclusive_scan(r->scan_tmp, tmp, r->touched, r->offsets, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
+    ENTRY_CHECK(hipMemcpyAsync(r->h_total, r->offsets + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    ENTRY_CHECK(hipStreamSynchronize(st));  // the one synchronisation of a frame
     total = *r->h_total;
     if (total > (uint64_t)INT32_MAX) return MPMHIP_ERR_LIMIT;
   } else if (int rc = mark(r, 1)) {
@@ -342,24 +333,24 @@ int forward_impl(mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, c
   if (int rc = mark(r, 2)) return rc;
   if (total > 0) {
     if (int rc = reserve_entries(r, (size_t)total)) return rc;
-    hipLaunchKernelGGL(k_raster_duplicate, blocks(n), TPB, 0, st, n, gx, (const int4 *)r->rect, (const float4 *)r->rec0,
+    hipLaunchKernelGGL(k_raster_duplicate, blocks(n, TPB), TPB, 0, st, n, gx, (const int4 *)r->rect, (const float4 *)r->rec0,
                        (const uint64_t *)r->offsets, r->keys[0], r->vals[0]);
-    RS_CHECK(hipGetLastError());
+    ENTRY_CHECK(hipGetLastError());
     if (int rc = mark(r, 3)) return rc;
     const unsigned end_bit = 32u + bits_for(tiles);
     size_t tmp = 0;
-    RS_CHECK(rocprim::radix_sort_pairs(nullptr, tmp, r->keys[0], r->keys[1], r->vals[0], r->vals[1], (size_t)total, 0u, end_bit, st));
+    ENTRY_CHECK(rocprim::radix_sort_pairs(nullptr, tmp, r->keys[0], r->keys[1], r->vals[0], r->vals[1], (size_t)total, 0u, end_bit, st));
     if (int rc = reserve_tmp(r, r->sort_tmp, r->sort_tmp_bytes, tmp)) return rc;
-    RS_CHECK(rocprim::radix_sort_pairs(r->sort_tmp, tmp, r->keys[0], r->keys[1], r->vals[0], r->vals[1], (size_t)total, 0u,
+    ENTRY_CHECK(rocprim::radix_sort_pairs(r->sort_tmp, tmp, r->keys[0], r->keys[1], r->vals[0], r->vals[1], (size_t)total, 0u,
                                        end_bit, st));
     if (int rc = mark(r, 4)) return rc;
-    hipLaunchKernelGGL(k_raster_ranges, blocks((int64_t)total), TPB, 0, st, (int64_t)total, (const uint64_t *)r->keys[1], r->ranges);
-    RS_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_raster_ranges, blocks((int64_t)total, TPB), TPB, 0, st, (int64_t)total, (const uint64_t *)r->keys[1], r->ranges);
+    ENTRY_CHECK(hipGetLastError());
     if (grad) {
       if (int rc = reserve_grad(r, (size_t)W * H, (size_t)total)) return rc;
-      hipLaunchKernelGGL(k_raster_inverse, blocks((int64_t)total), TPB, 0, st, (int64_t)total, gx, (const uint64_t *)r->keys[1],
+      hipLaunchKernelGGL(k_raster_inverse, blocks((int64_t)total, TPB), TPB, 0, st, (int64_t)total, gx, (const uint64_t *)r->keys[1],
                          (const uint32_t *)r->vals[1], (const int4 *)r->rect, (const uint64_t *)r->offsets, r->inv);
-      RS_CHECK(hipGetLastError());
+      ENTRY_CHECK(hipGetLastError());
     }
   } else {
     if (int rc = mark(r, 3)) return rc;
@@ -379,13 +370,13 @@ int forward_impl(mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, c
                        (const uint32_t *)r->vals[1], (const float4 *)r->rec0, (const float4 *)r->rec1, (const float *)r->colour,
                        s->bg[0], s->bg[1], s->bg[2], out_color, out_alpha, (float *)nullptr, (uint32_t *)nullptr);
   }
-  RS_CHECK(hipGetLastError());
+  ENTRY_CHECK(hipGetLastError());
   if (r->profile) {
     if (int rc = mark(r, 6)) return rc;
-    RS_CHECK(hipEventSynchronize(r->ev[6]));
+    ENTRY_CHECK(hipEventSynchronize(r->ev[6]));
     for (int k = 0; k < MPMHIP_RASTER_STAGES; ++k) {
       float ms = 0.f;
-      RS_CHECK(hipEventElapsedTime(&ms, r->ev[k], r->ev[k + 1]));
+      ENTRY_CHECK(hipEventElapsedTime(&ms, r->ev[k], r->ev[k + 1]));
       r->stage_ms[k] += ms;
     }
     ++r->profiled_frames;
@@ -399,12 +390,12 @@ extern "C" {
 
 int mpmhip_raster_profile(mpmhip_raster *r, int32_t on, double *stage_ms, int64_t *frames) {
   if (!r) return MPMHIP_ERR_INVALID;
-  RS_CHECK(hipSetDevice(r->device));
+  ENTRY_CHECK(hipSetDevice(r->device));
   if (stage_ms) for (int k = 0; k < MPMHIP_RASTER_STAGES; ++k) stage_ms[k] = r->stage_ms[k];
   if (frames) *frames = r->profiled_frames;
   if (on && !r->profile) {
     for (auto &e : r->ev)
-      if (!e) RS_CHECK(hipEventCreate(&e));
+      if (!e) ENTRY_CHECK(hipEventCreate(&e));
     for (double &v : r->stage_ms) v = 0.0;
     r->profiled_frames = 0;
   }
@@ -414,16 +405,16 @@ int mpmhip_raster_profile(mpmhip_raster *r, int32_t on, double *stage_ms, int64_
 
 int mpmhip_raster_stats(const mpmhip_raster *r, mpmhip_raster_stats_t *out) {
   if (!r || !out) return MPMHIP_ERR_INVALID;
-  RS_CHECK(hipSetDevice(r->device));
+  ENTRY_CHECK(hipSetDevice(r->device));
   int32_t counts[2] = {0, 0};
   if (r->last_tiles > 0) {
-    RS_CHECK(hipMemsetAsync(r->d_counts, 0, sizeof(counts), r->stream));
+    ENTRY_CHECK(hipMemsetAsync(r->d_counts, 0, sizeof(counts), r->stream));
     const int m = r->last_tiles > r->last_n ? r->last_tiles : r->last_n;
-    hipLaunchKernelGGL(k_raster_counts, blocks(m), TPB, 0, r->stream, r->last_tiles, (const uint2 *)r->ranges, r->last_n,
+    hipLaunchKernelGGL(k_raster_counts, blocks(m, TPB), TPB, 0, r->stream, r->last_tiles, (const uint2 *)r->ranges, r->last_n,
                        (const uint32_t *)r->touched, r->d_counts);
-    RS_CHECK(hipGetLastError());
-    RS_CHECK(hipMemcpyAsync(counts, r->d_counts, sizeof(counts), hipMemcpyDeviceToHost, r->stream));
-    RS_CHECK(hipStreamSynchronize(r->stream));
+    ENTRY_CHECK(hipGetLastError());
+    ENTRY_CHECK(hipMemcpyAsync(counts, r->d_counts, sizeof(counts), hipMemcpyDeviceToHost, r->stream));
+    ENTRY_CHECK(hipStreamSynchronize(r->stream));
   }
   out->n_entries = r->last_entries;
   out->max_tile_entries = counts[0];

@@ -104,10 +104,6 @@ __global__ __launch_bounds__(TPB) void k_raster_backward_tiles(int W, int H, int
   }
 }
 
-struct Inputs {  // of the forward call; exactly one of each alternative is non-NULL
-  const float *means, *shs, *colors, *opac, *scales, *rots, *cov;
-  int n_sh;
-};
 struct Grads {
   float *means, *means2d, *shs, *colors, *opac, *scales, *rots, *cov;
 };
@@ -178,7 +174,7 @@ __global__ __launch_bounds__(TPB) void k_raster_backward_gaussians(int n, Camera
 
 int reserve_rows(mpmhip_raster *r, size_t count) {
   if (count <= r->cap_rows) return MPMHIP_OK;
-  RS_CHECK(hipStreamSynchronize(r->stream));
+  ENTRY_CHECK(hipStreamSynchronize(r->stream));
   const size_t cap = grown(r->cap_rows, count);
   r->cap_rows = 0;
   if (int rc = regrow(r->rows, cap)) return rc;
@@ -194,28 +190,22 @@ extern "C" int mpmhip_raster_backward(mpmhip_raster *r, const mpmhip_raster_sett
                                       int64_t saved_bytes, int64_t n_entries, const float *dL_dimage, const float *dL_dalpha,
                                       float *d_means3D, float *d_means2D, float *d_shs, float *d_colors_precomp, float *d_opacities,
                                       float *d_scales, float *d_rotations, float *d_cov3D_precomp) {
-  if (!r || !s || n < 0 || s->image_height <= 0 || s->image_width <= 0 || !saved) return MPMHIP_ERR_INVALID;
-  if (!s->viewmatrix || !s->projmatrix || !s->campos) return MPMHIP_ERR_INVALID;
-  if (n_entries < 0 || n_entries > (int64_t)INT32_MAX) return MPMHIP_ERR_INVALID;
+  if (!saved || n_entries < 0 || n_entries > (int64_t)INT32_MAX) return MPMHIP_ERR_INVALID;
   if (n > 0) {
-    if (!means3D || !opacities || !d_means3D || !d_means2D || !d_opacities) return MPMHIP_ERR_INVALID;
-    if ((shs != nullptr) == (colors_precomp != nullptr)) return MPMHIP_ERR_INVALID;
-    const bool sr = scales && rotations;
-    if ((scales != nullptr) != (rotations != nullptr) || sr == (cov3D_precomp != nullptr)) return MPMHIP_ERR_INVALID;
-    if (shs && (s->sh_degree < 0 || s->sh_degree > 3 || n_sh_coeffs < (s->sh_degree + 1) * (s->sh_degree + 1))) return MPMHIP_ERR_INVALID;
+    if (!d_means3D || !d_means2D || !d_opacities) return MPMHIP_ERR_INVALID;
     if (shs ? !d_shs : !d_colors_precomp) return MPMHIP_ERR_INVALID;
-    if (sr ? (!d_scales || !d_rotations) : !d_cov3D_precomp) return MPMHIP_ERR_INVALID;
+    if (scales && rotations ? (!d_scales || !d_rotations) : !d_cov3D_precomp) return MPMHIP_ERR_INVALID;
   } else if (n_entries != 0) {
     return MPMHIP_ERR_INVALID;
   }
-  const int W = s->image_width, H = s->image_height;
-  const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-  if ((int64_t)gx * gy > INT32_MAX || gy > 65535) return MPMHIP_ERR_LIMIT;
-  const int tiles = gx * gy;
+  const Inputs in{means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, n_sh_coeffs};
+  int gx = 0, gy = 0;
+  if (int rc = validate_frame(r, s, n, in, &gx, &gy)) return rc;
+  const int W = s->image_width, H = s->image_height, tiles = gx * gy;
   const SavedLayout l = saved_layout((size_t)n, (size_t)tiles, (size_t)W * H, (size_t)n_entries);
   if (saved_bytes != (int64_t)l.bytes) return MPMHIP_ERR_INVALID;  // another n, image size or entry count than the frame's
   if (n == 0) return MPMHIP_OK;                                     // nothing to write
-  RS_CHECK(hipSetDevice(r->device));
+  ENTRY_CHECK(hipSetDevice(r->device));
   hipStream_t st = r->stream;
   const char *sv = (const char *)saved;
   if (n_entries > 0) {
@@ -224,14 +214,13 @@ extern "C" int mpmhip_raster_backward(mpmhip_raster *r, const mpmhip_raster_sett
                        (uint32_t)n, (const uint2 *)(sv + l.ranges), (const uint32_t *)(sv + l.vals), (const float4 *)(sv + l.rec0),
                        (const float4 *)(sv + l.rec1), (const float *)(sv + l.colour), (const float *)(sv + l.pix_T),
                        (const uint32_t *)(sv + l.pix_stop), s->bg[0], s->bg[1], s->bg[2], dL_dimage, dL_dalpha, r->rows);
-    RS_CHECK(hipGetLastError());
+    ENTRY_CHECK(hipGetLastError());
   }
   Camera cam{W, H, gx, gy, s->tanfovx, s->tanfovy, s->scale_modifier, s->sh_degree, s->viewmatrix, s->projmatrix, s->campos};
-  Inputs in{means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, n_sh_coeffs};
   Grads out{d_means3D, d_means2D, d_shs, d_colors_precomp, d_opacities, d_scales, d_rotations, d_cov3D_precomp};
-  hipLaunchKernelGGL(k_raster_backward_gaussians, blocks(n), TPB, 0, st, n, cam, in, (const int4 *)(sv + l.rect),
+  hipLaunchKernelGGL(k_raster_backward_gaussians, blocks(n, TPB), TPB, 0, st, n, cam, in, (const int4 *)(sv + l.rect),
                      (const uint64_t *)(sv + l.offsets), (const uint32_t *)(sv + l.inv), (uint32_t)n_entries,
                      (const float *)r->rows, out);
-  RS_CHECK(hipGetLastError());
+  ENTRY_CHECK(hipGetLastError());
   return MPMHIP_OK;
 }

@@ -5,7 +5,7 @@
 
 #include <cstdint>
 
-#include "../../include/mpmhip.h"
+#include "entry.hpp"
 #include "raster_grad_math.hpp"
 
 struct mpmhip_raster {
@@ -56,6 +56,7 @@ struct mpmhip_raster {
 
 namespace raster_host {
 
+using namespace entry;
 constexpr int TPB = 256;
 constexpr int TILE = rast::TILE;
 static_assert(TILE * TILE == TPB, "one lane per pixel of a tile");
@@ -90,14 +91,33 @@ inline SavedLayout saved_layout(size_t n, size_t tiles, size_t pixels, size_t en
   return l;
 }
 
-inline int check(hipError_t e) { return e == hipSuccess ? MPMHIP_OK : MPMHIP_ERR_HIP; }
-#define RS_CHECK(expr) do { if (int rc_ = check(expr)) return rc_; } while (0)
+struct Inputs {  // of the forward call; exactly one of each alternative is non-NULL
+  const float *means, *shs, *colors, *opac, *scales, *rots, *cov;
+  int n_sh;
+};
 
-inline unsigned blocks(int64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
+// What mpmhip_raster_forward* and mpmhip_raster_backward ask of a frame alike: handle, settings and the input alternatives
+// (MPMHIP_ERR_INVALID), then the tile grid (MPMHIP_ERR_LIMIT).  The caller checks its own outputs BEFORE this, so that a
+// missing output stays MPMHIP_ERR_INVALID on a frame that is also too large.
+inline int validate_frame(const mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, const Inputs &in, int *gx, int *gy) {
+  if (!r || !s || n < 0 || s->image_height <= 0 || s->image_width <= 0) return MPMHIP_ERR_INVALID;
+  if (!s->viewmatrix || !s->projmatrix || !s->campos) return MPMHIP_ERR_INVALID;
+  if (n > 0) {
+    if (!in.means || !in.opac) return MPMHIP_ERR_INVALID;
+    if ((in.shs != nullptr) == (in.colors != nullptr)) return MPMHIP_ERR_INVALID;
+    const bool sr = in.scales && in.rots;
+    if ((in.scales != nullptr) != (in.rots != nullptr) || sr == (in.cov != nullptr)) return MPMHIP_ERR_INVALID;
+    if (in.shs && (s->sh_degree < 0 || s->sh_degree > 3 || in.n_sh < (s->sh_degree + 1) * (s->sh_degree + 1))) return MPMHIP_ERR_INVALID;
+  }
+  *gx = (s->image_width + TILE - 1) / TILE;
+  *gy = (s->image_height + TILE - 1) / TILE;
+  if ((int64_t)*gx * *gy > INT32_MAX || *gy > 65535) return MPMHIP_ERR_LIMIT;
+  return MPMHIP_OK;
+}
 
 template <class T>
 inline int regrow(T *&p, size_t count) {
-  if (p) RS_CHECK(hipFree(p));
+  if (p) ENTRY_CHECK(hipFree(p));
   p = nullptr;
   return check(hipMalloc((void **)&p, count * sizeof(T)));
 }
@@ -109,7 +129,7 @@ inline I grown(I cap, I need) { return need > 2 * cap ? need : 2 * cap; }
 // temporary storage of a rocPRIM call: asked for with the call's own arguments every frame (a host-side computation)
 inline int reserve_tmp(mpmhip_raster *r, void *&p, size_t &have, size_t need) {
   if (need <= have) return MPMHIP_OK;
-  RS_CHECK(hipStreamSynchronize(r->stream));
+  ENTRY_CHECK(hipStreamSynchronize(r->stream));
   const size_t cap = grown(have, need);
   char *tmp = (char *)p;
   p = nullptr;
@@ -122,7 +142,7 @@ inline int reserve_tmp(mpmhip_raster *r, void *&p, size_t &have, size_t need) {
 
 inline int reserve_gaussians(mpmhip_raster *r, int n) {
   if (n <= r->cap_n) return MPMHIP_OK;
-  RS_CHECK(hipStreamSynchronize(r->stream));  // nothing in flight may still read what is freed
+  ENTRY_CHECK(hipStreamSynchronize(r->stream));  // nothing in flight may still read what is freed
   const int cap = grown(r->cap_n, n);
   r->cap_n = 0;
   if (int rc = regrow(r->rec0, (size_t)cap)) return rc;
@@ -137,7 +157,7 @@ inline int reserve_gaussians(mpmhip_raster *r, int n) {
 
 inline int reserve_entries(mpmhip_raster *r, size_t total) {
   if (total <= r->cap_e) return MPMHIP_OK;
-  RS_CHECK(hipStreamSynchronize(r->stream));
+  ENTRY_CHECK(hipStreamSynchronize(r->stream));
   const size_t cap = grown(r->cap_e, total);
   r->cap_e = 0;
   for (int k = 0; k < 2; ++k) {
@@ -150,7 +170,7 @@ inline int reserve_entries(mpmhip_raster *r, size_t total) {
 
 inline int reserve_tiles(mpmhip_raster *r, int tiles) {
   if (tiles <= r->cap_tiles) return MPMHIP_OK;
-  RS_CHECK(hipStreamSynchronize(r->stream));
+  ENTRY_CHECK(hipStreamSynchronize(r->stream));
   const int cap = grown(r->cap_tiles, tiles);
   r->cap_tiles = 0;
   if (int rc = regrow(r->ranges, (size_t)cap)) return rc;

@@ -16,42 +16,28 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib as L
 from . import io_formats
+from ._call import call, expect, ptr
 
 TAU = 1e-3                 # metric.py:60
 REDUCE_SCRATCH = 256       # MPMHIP_GEO_REDUCE_SCRATCH
 
 
-def _chk(t, dtype, name, shape_last=None):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
-        raise RuntimeError(f"{name}: expected a contiguous {dtype} tensor on the GPU")
-    if shape_last is not None and (t.dim() != 2 or t.shape[-1] != shape_last or t.shape[0] == 0):
-        raise RuntimeError(f"{name}: expected a non-empty [n, {shape_last}] tensor")
-    return t
-
-
-def _call(name, dev, *args):
-    rc = getattr(L.load(), name)(dev.index or 0, torch.cuda.current_stream(dev).cuda_stream, *args)
-    if rc != L.OK:
-        raise L.MPMHipError(rc, f"{name} failed")
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+def _chk(t, dtype, name, last=None):
+    return expect(t, dtype, name, last=last, rows=True)
 
 
 def face_area_cdf(verts, faces):
     """(area [n_f] float32, inclusive cumulative sum [n_f] float64) of the mesh's faces."""
     v, f = _chk(verts, torch.float32, "verts", 3), _chk(faces, torch.int32, "faces", 3)
     area = torch.empty(f.shape[0], dtype=torch.float32, device=v.device)
-    _call("mpmhip_face_areas", v.device, v.data_ptr(), f.data_ptr(), f.shape[0], area.data_ptr())
+    call("mpmhip_face_areas", v.device, v.data_ptr(), f.data_ptr(), f.shape[0], area.data_ptr())
     return area, torch.cumsum(area.double(), 0)
 
 
 def _sample_into(verts, faces, cdf, uniforms, points, face_index):
-    _call("mpmhip_mesh_sample", verts.device, verts.data_ptr(), faces.data_ptr(), faces.shape[0], cdf.data_ptr(),
-          uniforms.data_ptr(), uniforms.shape[0], points.data_ptr(), _ptr(face_index))
+    call("mpmhip_mesh_sample", verts.device, verts.data_ptr(), faces.data_ptr(), faces.shape[0], cdf.data_ptr(),
+         uniforms.data_ptr(), uniforms.shape[0], points.data_ptr(), ptr(face_index))
 
 
 def sample_surface(verts, faces, count, generator=None):
@@ -70,8 +56,8 @@ def sample_surface(verts, faces, count, generator=None):
 
 
 def _nn_into(src, dst, slices, best, dist2, index):
-    _call("mpmhip_nn_dist2", src.device, src.data_ptr(), src.shape[0], dst.data_ptr(), dst.shape[0], slices, best.data_ptr(),
-          dist2.data_ptr(), _ptr(index))
+    call("mpmhip_nn_dist2", src.device, src.data_ptr(), src.shape[0], dst.data_ptr(), dst.shape[0], slices, best.data_ptr(),
+         dist2.data_ptr(), ptr(index))
 
 
 def nearest_dist2(src, dst, return_index=False, slices=0):
@@ -89,8 +75,8 @@ def nearest_dist2(src, dst, return_index=False, slices=0):
 
 
 def _reduce_into(d12, d21, tau, scratch, out):
-    _call("mpmhip_geo_reduce", d12.device, d12.data_ptr(), d12.shape[0], d21.data_ptr(), d21.shape[0], float(tau),
-          scratch.data_ptr(), out.data_ptr())
+    call("mpmhip_geo_reduce", d12.device, d12.data_ptr(), d12.shape[0], d21.data_ptr(), d21.shape[0], float(tau),
+         scratch.data_ptr(), out.data_ptr())
 
 
 def reduce_dist2(dist2_12, dist2_21, tau=TAU):

@@ -41,23 +41,16 @@ import os
 import numpy as np
 import torch
 
-from . import _lib as L
+from ._call import call, expect, ptr, upstream
 
 WINDOW_SIZE = 11
 
 
 def _chk(t, name):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
-        raise RuntimeError(f"{name}: expected a torch.float32 tensor on the GPU")
+    expect(t, torch.float32, name, contiguous=False)
     if t.dim() not in (3, 4) or t.numel() == 0:
         raise RuntimeError(f"{name}: expected a non-empty [C, H, W] or [N, C, H, W] tensor, got {tuple(t.shape)}")
     return t
-
-
-def _call(name, dev, *args):
-    rc = getattr(L.load(), name)(dev.index or 0, torch.cuda.current_stream(dev).cuda_stream, *args)
-    if rc != L.OK:
-        raise L.MPMHipError(rc, f"{name} failed")
 
 
 def scratch_doubles(planes, H, W):
@@ -76,8 +69,8 @@ class _PlaneMeans(torch.autograd.Function):
         maps = torch.empty((planes, 3, H, W), dtype=torch.float32, device=dev) if want_grad else None
         scratch = torch.empty(scratch_doubles(planes, H, W), dtype=torch.float64, device=dev)
         out = torch.empty((planes, 3), dtype=torch.float32, device=dev)
-        _call("mpmhip_image_loss_forward", dev, img.data_ptr(), gt.data_ptr(), planes, H, W,
-              None if maps is None else maps.data_ptr(), scratch.data_ptr(), out.data_ptr())
+        call("mpmhip_image_loss_forward", dev, img.data_ptr(), gt.data_ptr(), planes, H, W,
+             ptr(maps), scratch.data_ptr(), out.data_ptr())
         if want_grad:
             ctx.save_for_backward(img, gt, maps)
         return out[:, 0].contiguous(), out[:, 1].contiguous(), out[:, 2].contiguous()
@@ -87,11 +80,10 @@ class _PlaneMeans(torch.autograd.Function):
     def backward(ctx, g_l1, g_mse, g_ssim):
         img, gt, maps = ctx.saved_tensors
         planes, H, W = img.shape
-        g = [torch.zeros(planes, dtype=torch.float32, device=img.device) if t is None else t.to(torch.float32).contiguous()
-             for t in (g_l1, g_mse, g_ssim)]
+        g = [torch.zeros(planes, dtype=torch.float32, device=img.device) if t is None else upstream(t) for t in (g_l1, g_mse, g_ssim)]
         d_img = torch.empty_like(img)
-        _call("mpmhip_image_loss_backward", img.device, img.data_ptr(), gt.data_ptr(), planes, H, W, maps.data_ptr(),
-              g[0].data_ptr(), g[1].data_ptr(), g[2].data_ptr(), d_img.data_ptr())
+        call("mpmhip_image_loss_backward", img.device, img.data_ptr(), gt.data_ptr(), planes, H, W, maps.data_ptr(),
+             g[0].data_ptr(), g[1].data_ptr(), g[2].data_ptr(), d_img.data_ptr())
         return d_img, None, None
 
 

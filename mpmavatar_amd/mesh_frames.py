@@ -22,6 +22,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib as L
+from ._call import call, expect, ptr, upstream, wants_grad
 
 
 def _csr(keys, n_keys, what):
@@ -36,47 +37,31 @@ def _csr(keys, n_keys, what):
     return start, torch.sort(k, stable=True).indices.to(torch.int32)
 
 
-def _wants_grad(*tensors):
-    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
-
-
-def _call(lib, name, *args):
-    rc = getattr(lib, name)(*args)
-    if rc != L.OK:
-        raise L.MPMHipError(rc, f"{name} failed")
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _launch_face_frames(lib, faces, v):
+def _launch_face_frames(faces, v):
     n_f = faces.shape[0]
     dev = v.device
     new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
     center, mat, quat, scale = new(n_f, 3), new(n_f, 3, 3), new(n_f, 4), new(n_f, 1)
-    _call(lib, "mpmhip_face_frames", dev.index or 0, torch.cuda.current_stream(dev).cuda_stream, v.data_ptr(), faces.data_ptr(), n_f,
-          center.data_ptr(), mat.data_ptr(), quat.data_ptr(), scale.data_ptr())
+    call("mpmhip_face_frames", dev, v.data_ptr(), faces.data_ptr(), n_f, center.data_ptr(), mat.data_ptr(), quat.data_ptr(), scale.data_ptr())
     return center, mat, quat, scale
 
 
-def _launch_bind(lib, render, means2D, binding, frame, params, extra):
+def _launch_bind(render, means2D, binding, frame, params, extra):
     """One launch of the binding: mpmhip_render_inputs (``render``: all four parameters, n + m rows with the ``extra`` tensors behind,
     means2D cleared through its pointer) or mpmhip_bind_gaussians (any of xyz / rotation / scaling).  -> (means3D / xyz, rotations,
     scales, opacities), None where a parameter was not given."""
     dev = binding.device
     n, m = binding.numel(), (0 if extra[0] is None else extra[0].shape[0])
-    stream = torch.cuda.current_stream(dev).cuda_stream
     o_xyz, o_rot, o_scl, o_opa = [None if t is None else torch.empty(n + m, w, dtype=torch.float32, device=dev)
                                   for t, w in zip(params, (3, 4, 3, 1))]
     xyz, rot, scl, opa = params
     if render:
-        _call(lib, "mpmhip_render_inputs", dev.index or 0, stream, n, m, binding.data_ptr(), xyz.data_ptr(), rot.data_ptr(),
-              scl.data_ptr(), opa.data_ptr(), *[t.data_ptr() for t in frame], *[_ptr(t) for t in extra], o_xyz.data_ptr(), means2D,
-              o_opa.data_ptr(), o_scl.data_ptr(), o_rot.data_ptr())
+        call("mpmhip_render_inputs", dev, n, m, binding.data_ptr(), xyz.data_ptr(), rot.data_ptr(), scl.data_ptr(), opa.data_ptr(),
+             *[t.data_ptr() for t in frame], *[ptr(t) for t in extra], o_xyz.data_ptr(), means2D, o_opa.data_ptr(), o_scl.data_ptr(),
+             o_rot.data_ptr())
     else:
-        _call(lib, "mpmhip_bind_gaussians", dev.index or 0, stream, n, binding.data_ptr(), _ptr(xyz), _ptr(rot), _ptr(scl),
-              *[t.data_ptr() for t in frame], _ptr(o_xyz), _ptr(o_rot), _ptr(o_scl))
+        call("mpmhip_bind_gaussians", dev, n, binding.data_ptr(), ptr(xyz), ptr(rot), ptr(scl), *[t.data_ptr() for t in frame],
+             ptr(o_xyz), ptr(o_rot), ptr(o_scl))
     return o_xyz, o_rot, o_scl, o_opa
 
 
@@ -84,9 +69,9 @@ class _FaceFrames(torch.autograd.Function):
     """verts -> (face_center, face_orien_mat, face_orien_quat, face_scaling): the forward launch of set_mesh_by_verts with a backward."""
 
     @staticmethod
-    def forward(ctx, verts, lib, faces, vtable):
-        out = _launch_face_frames(lib, faces, verts)
-        ctx.lib, ctx.faces, ctx.vtable = lib, faces, vtable
+    def forward(ctx, verts, faces, vtable):
+        out = _launch_face_frames(faces, verts)
+        ctx.faces, ctx.vtable = faces, vtable
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(verts, out[1], out[2])
         return out
@@ -98,13 +83,12 @@ class _FaceFrames(torch.autograd.Function):
         faces = ctx.faces
         n_f, n_v, dev = faces.shape[0], verts.shape[0], verts.device
         start, corners = ctx.vtable.get(faces, n_v)
-        g = [None if t is None else t.to(torch.float32).contiguous() for t in (g_center, g_mat, g_quat, g_scale)]
+        g = [upstream(t) for t in (g_center, g_mat, g_quat, g_scale)]
         d_corners = torch.empty(n_f, 3, 3, dtype=torch.float32, device=dev)
         d_verts = torch.empty_like(verts)
-        _call(ctx.lib, "mpmhip_face_frames_backward", dev.index or 0, torch.cuda.current_stream(dev).cuda_stream, verts.data_ptr(),
-              faces.data_ptr(), n_f, n_v, mat.data_ptr(), quat.data_ptr(), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(g[3]),
-              start.data_ptr(), corners.data_ptr(), d_corners.data_ptr(), d_verts.data_ptr())
-        return d_verts, None, None, None
+        call("mpmhip_face_frames_backward", dev, verts.data_ptr(), faces.data_ptr(), n_f, n_v, mat.data_ptr(), quat.data_ptr(),
+             *[ptr(t) for t in g], start.data_ptr(), corners.data_ptr(), d_corners.data_ptr(), d_verts.data_ptr())
+        return d_verts, None, None
 
 
 class _Bind(torch.autograd.Function):
@@ -114,10 +98,10 @@ class _Bind(torch.autograd.Function):
     keyed on; means2D is written through its pointer and is no part of the graph."""
 
     @staticmethod
-    def forward(ctx, lib, table, key, render, means2D, binding, center, mat, quat, fscale, xyz, rot, scl, opa, x_xyz, x_opa, x_scl, x_rot):
-        out = _launch_bind(lib, render, means2D, binding, (center, mat, quat, fscale), (xyz, rot, scl, opa), (x_xyz, x_opa, x_scl, x_rot))
+    def forward(ctx, table, key, render, means2D, binding, center, mat, quat, fscale, xyz, rot, scl, opa, x_xyz, x_opa, x_scl, x_rot):
+        out = _launch_bind(render, means2D, binding, (center, mat, quat, fscale), (xyz, rot, scl, opa), (x_xyz, x_opa, x_scl, x_rot))
         n = binding.numel()
-        ctx.lib, ctx.table, ctx.n, ctx.n_f = lib, table, n, fscale.shape[0]
+        ctx.table, ctx.n, ctx.n_f = table, n, fscale.shape[0]
         ctx.key = (key, key.data_ptr(), key._version)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(binding, mat, quat, fscale, xyz, rot, scl, opa)
@@ -128,26 +112,24 @@ class _Bind(torch.autograd.Function):
     def backward(ctx, g_xyz, g_rot, g_scl, g_opa):
         binding, mat, quat, fscale, xyz, rot, scl, opa = ctx.saved_tensors
         n, n_f, dev = ctx.n, ctx.n_f, binding.device
-        need = ctx.needs_input_grad
-        g = [None if t is None else t.to(torch.float32).contiguous() for t in (g_xyz, g_rot, g_scl, g_opa)]
-        out = lambda want, t: torch.empty_like(t) if want and t is not None else None
-        d_xyz, d_rot, d_scl, d_opa = out(need[10], xyz), out(need[11], rot), out(need[12], scl), out(need[13], opa)
+        need_face, need_param, need_extra = ctx.needs_input_grad[5:9], ctx.needs_input_grad[9:13], ctx.needs_input_grad[13:17]
+        g = [upstream(t) for t in (g_xyz, g_rot, g_scl, g_opa)]
+        d_xyz, d_rot, d_scl, d_opa = [torch.empty_like(t) if want and t is not None else None
+                                      for want, t in zip(need_param, (xyz, rot, scl, opa))]
         d_face = [None] * 4
         start = items = None
-        if any(need[6:10]):
+        if any(need_face):
             start, items = ctx.table.get(ctx.key, binding, n_f)
             d_face = [torch.empty(n_f, w, dtype=torch.float32, device=dev) for w in (3, 9, 4, 1)]
-        _call(ctx.lib, "mpmhip_render_inputs_backward", dev.index or 0, torch.cuda.current_stream(dev).cuda_stream, n, n_f,
-              binding.data_ptr(), _ptr(xyz), _ptr(rot), _ptr(scl), _ptr(opa), mat.data_ptr(), quat.data_ptr(), fscale.data_ptr(),
-              _ptr(g[0]), _ptr(g[3]), _ptr(g[2]), _ptr(g[1]), _ptr(d_xyz), _ptr(d_rot), _ptr(d_scl), _ptr(d_opa), _ptr(start), _ptr(items),
-              *[_ptr(t) for t in d_face])
-        d_center, d_mat, d_quat, d_fscale = [t if want else None for t, want in zip(d_face, need[6:10])]
+        call("mpmhip_render_inputs_backward", dev, n, n_f, binding.data_ptr(), ptr(xyz), ptr(rot), ptr(scl), ptr(opa), mat.data_ptr(),
+             quat.data_ptr(), fscale.data_ptr(), ptr(g[0]), ptr(g[3]), ptr(g[2]), ptr(g[1]), ptr(d_xyz), ptr(d_rot), ptr(d_scl), ptr(d_opa),
+             ptr(start), ptr(items), *[ptr(t) for t in d_face])
+        d_center, d_mat, d_quat, d_fscale = [t if want else None for t, want in zip(d_face, need_face)]
         if d_mat is not None:
             d_mat = d_mat.view(n_f, 3, 3)
         # the rows behind the bound Gaussians are the `extra` tensors copied: their gradients are the upstream rows
-        tail = lambda want, t: t[n:] if want and t is not None else None
-        return (None, None, None, None, None, None, d_center, d_mat, d_quat, d_fscale, d_xyz, d_rot, d_scl, d_opa,
-                tail(need[14], g[0]), tail(need[15], g[3]), tail(need[16], g[2]), tail(need[17], g[1]))
+        tails = [t[n:] if want and t is not None else None for want, t in zip(need_extra, (g[0], g[3], g[2], g[1]))]
+        return (None, None, None, None, None, d_center, d_mat, d_quat, d_fscale, d_xyz, d_rot, d_scl, d_opa, *tails)
 
 
 class _GaussianTable:
@@ -178,46 +160,38 @@ class _VertexTable:
         return self._t[1:]
 
 
-def _chk(t, dtype, name, shape_last=None):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
-        raise RuntimeError(f"{name}: expected a contiguous {dtype} tensor on the GPU")
-    if shape_last is not None and (t.dim() < 1 or t.shape[-1] != shape_last):
-        raise RuntimeError(f"{name}: last dimension must be {shape_last}")
-    return t
-
-
 class MeshFrames:
     def __init__(self, faces: torch.Tensor):
-        self.faces = _chk(faces.to(torch.int32).contiguous(), torch.int32, "faces", 3)
-        self._lib = L.load()
+        self.faces = expect(faces.to(torch.int32).contiguous(), torch.int32, "faces", last=3)
+        L.load()                                 # a missing library is reported here, not at the first launch
         self._vtable, self._gtable = _VertexTable(), _GaussianTable()
         self.verts = None
         self.face_center = self.face_orien_mat = self.face_orien_quat = self.face_scaling = None
 
     # mesh_gaussian_model.py:137-146
     def set_mesh_by_verts(self, verts: torch.Tensor):
-        v = _chk(verts, torch.float32, "verts", 3)
+        v = expect(verts, torch.float32, "verts", last=3)
         if v.device != self.faces.device:
             raise RuntimeError("verts and faces must be on the same device")
         self.verts = v
-        if _wants_grad(v):
-            out = _FaceFrames.apply(v, self._lib, self.faces, self._vtable)
+        if wants_grad(v):
+            out = _FaceFrames.apply(v, self.faces, self._vtable)
         else:
-            out = _launch_face_frames(self._lib, self.faces, v)
+            out = _launch_face_frames(self.faces, v)
         self.face_center, self.face_orien_mat, self.face_orien_quat, self.face_scaling = out
 
     def _bind(self, binding, xyz_local=None, rotation=None, scaling=None):
         if self.face_center is None:
             raise RuntimeError("call set_mesh_by_verts first")
-        b = _chk(binding.to(torch.int32).contiguous(), torch.int32, "binding")
+        b = expect(binding.to(torch.int32).contiguous(), torch.int32, "binding")
         for t, name, w in ((xyz_local, "_xyz", 3), (rotation, "_rotation", 4), (scaling, "_scaling", 3)):
             if t is not None:
-                _chk(t, torch.float32, name, w)
+                expect(t, torch.float32, name, last=w)
         fr = (self.face_center, self.face_orien_mat, self.face_orien_quat, self.face_scaling)
-        if _wants_grad(xyz_local, rotation, scaling, *fr):
-            out = _Bind.apply(self._lib, self._gtable, binding, False, None, b, *fr, xyz_local, rotation, scaling, None, None, None, None, None)
+        if wants_grad(xyz_local, rotation, scaling, *fr):
+            out = _Bind.apply(self._gtable, binding, False, None, b, *fr, xyz_local, rotation, scaling, None, None, None, None, None)
         else:
-            out = _launch_bind(self._lib, False, None, b, fr, (xyz_local, rotation, scaling, None), (None,) * 4)
+            out = _launch_bind(False, None, b, fr, (xyz_local, rotation, scaling, None), (None,) * 4)
         return list(out[:3])
 
     # gaussian_model.py:141-151 / :124-138 / :112-122 (binding is not None branch)

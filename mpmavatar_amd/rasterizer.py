@@ -50,6 +50,7 @@ from typing import NamedTuple
 import torch
 
 from . import _lib as L
+from ._call import call_handle, expect, ptr, upstream
 
 
 class GaussianRasterizationSettings(NamedTuple):  # fields and order of gaussian_renderer/__init__.py:36-49
@@ -67,14 +68,6 @@ class GaussianRasterizationSettings(NamedTuple):  # fields and order of gaussian
     debug: bool
 
 
-def _chk(t, dtype, name, shape=None):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
-        raise RuntimeError(f"{name}: expected a contiguous {dtype} tensor on the GPU")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
-    return t
-
-
 class _Handle:
     """One mpmhip_raster per (device, stream): the scratch is reused from frame to frame.  The handle keeps the
     torch.cuda.Stream object it was made for: torch's own streams come from a pool that is never destroyed, and for an
@@ -86,9 +79,7 @@ class _Handle:
         self.ptr = L.vp()
         self.stream = stream
         self.last_user = None     # weak reference to the rasteriser whose frame the handle's counts describe
-        rc = self.lib.mpmhip_raster_create(device_index, stream.cuda_stream, C.byref(self.ptr))
-        if rc != L.OK:
-            raise L.MPMHipError(rc, "mpmhip_raster_create failed")
+        call_handle("mpmhip_raster_create", device_index, stream.cuda_stream, C.byref(self.ptr))
         weakref.finalize(self, self.lib.mpmhip_raster_destroy, self.ptr)
 
 
@@ -134,29 +125,36 @@ class _Frame:
     __slots__ = ("cs", "keep", "hd", "n", "n_sh", "saved", "n_entries", "h", "w")
 
 
+def _ptr(t):
+    """the rasteriser's own rule on top of ptr: an empty tensor goes down as NULL too"""
+    return None if t is not None and t.numel() == 0 else ptr(t)
+
+
+def _launch_forward(hd, cs, n, n_sh, tensors, grad):
+    """One frame: allocates image [3, H, W], alpha [1, H, W] and radii [n] and runs mpmhip_raster_forward, or with ``grad``
+    mpmhip_raster_forward_grad.  tensors = (means3D, shs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)."""
+    dev, h, w = tensors[0].device, cs.image_height, cs.image_width
+    image = torch.empty(3, h, w, dtype=torch.float32, device=dev)
+    alpha = torch.empty(1, h, w, dtype=torch.float32, device=dev)
+    radii = torch.empty(n, dtype=torch.int32, device=dev)
+    means3D, shs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp = map(_ptr, tensors)
+    call_handle("mpmhip_raster_forward_grad" if grad else "mpmhip_raster_forward", hd.ptr, C.byref(cs), n, means3D, shs, n_sh,
+                colors_precomp, opacities, scales, rotations, cov3Ds_precomp, image.data_ptr(), alpha.data_ptr(), _ptr(radii))
+    return image, alpha, radii
+
+
 class _Rasterize(torch.autograd.Function):
     """forward: mpmhip_raster_forward_grad + mpmhip_raster_save; backward: mpmhip_raster_backward"""
 
     @staticmethod
     def forward(ctx, fr, means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3Ds_precomp):
-        hd, dev = fr.hd, means3D.device
-        image = torch.empty(3, fr.h, fr.w, dtype=torch.float32, device=dev)
-        alpha = torch.empty(1, fr.h, fr.w, dtype=torch.float32, device=dev)
-        radii = torch.empty(fr.n, dtype=torch.int32, device=dev)
-        p = _ptr
-        rc = hd.lib.mpmhip_raster_forward_grad(hd.ptr, C.byref(fr.cs), fr.n, p(means3D), p(shs), fr.n_sh, p(colors_precomp), p(opacities),
-                                               p(scales), p(rotations), p(cov3Ds_precomp), image.data_ptr(), alpha.data_ptr(), p(radii))
-        if rc != L.OK:
-            raise L.MPMHipError(rc, "mpmhip_raster_forward_grad failed")
+        hd, tensors = fr.hd, (means3D, shs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+        image, alpha, radii = _launch_forward(hd, fr.cs, fr.n, fr.n_sh, tensors, True)
         size, entries = C.c_int64(), C.c_int64()
-        rc = hd.lib.mpmhip_raster_saved_bytes(hd.ptr, C.byref(size), C.byref(entries))
-        if rc != L.OK:
-            raise L.MPMHipError(rc, "mpmhip_raster_saved_bytes failed")
-        fr.saved = torch.empty(size.value, dtype=torch.uint8, device=dev)
+        call_handle("mpmhip_raster_saved_bytes", hd.ptr, C.byref(size), C.byref(entries))
+        fr.saved = torch.empty(size.value, dtype=torch.uint8, device=means3D.device)
         fr.n_entries = entries.value
-        rc = hd.lib.mpmhip_raster_save(hd.ptr, fr.saved.data_ptr(), size.value)
-        if rc != L.OK:
-            raise L.MPMHipError(rc, "mpmhip_raster_save failed")
+        call_handle("mpmhip_raster_save", hd.ptr, fr.saved.data_ptr(), size.value)
         ctx.fr = fr
         ctx.means2D_shape = None if means2D is None else tuple(means2D.shape)
         ctx.save_for_backward(means3D, opacities, shs, colors_precomp, scales, rotations, cov3Ds_precomp)
@@ -170,27 +168,19 @@ class _Rasterize(torch.autograd.Function):
         fr = ctx.fr
         means3D, opacities, shs, colors_precomp, scales, rotations, cov3Ds_precomp = ctx.saved_tensors
         hd, dev, n = fr.hd, means3D.device, fr.n
-        grad_in = lambda g, shape: None if g is None else g.to(torch.float32).expand(shape).contiguous()
-        g_image, g_alpha = grad_in(g_image, (3, fr.h, fr.w)), grad_in(g_alpha, (1, fr.h, fr.w))
+        g_image, g_alpha = upstream(g_image, (3, fr.h, fr.w)), upstream(g_alpha, (1, fr.h, fr.w))
         like = lambda t: None if t is None else torch.empty_like(t)
         d_means3D, d_means2D, d_opac = torch.empty_like(means3D), torch.empty(n, 3, dtype=torch.float32, device=dev), torch.empty_like(opacities)
         d_shs, d_col, d_scales, d_rots, d_cov = like(shs), like(colors_precomp), like(scales), like(rotations), like(cov3Ds_precomp)
         p = _ptr
-        rc = hd.lib.mpmhip_raster_backward(hd.ptr, C.byref(fr.cs), n, p(means3D), p(shs), fr.n_sh, p(colors_precomp), p(opacities), p(scales),
-                                           p(rotations), p(cov3Ds_precomp), fr.saved.data_ptr(), fr.saved.numel(), fr.n_entries,
-                                           p(g_image), p(g_alpha), p(d_means3D), p(d_means2D), p(d_shs), p(d_col), p(d_opac),
-                                           p(d_scales), p(d_rots), p(d_cov))
-        if rc != L.OK:
-            raise L.MPMHipError(rc, "mpmhip_raster_backward failed")
+        call_handle("mpmhip_raster_backward", hd.ptr, C.byref(fr.cs), n, p(means3D), p(shs), fr.n_sh, p(colors_precomp), p(opacities),
+                    p(scales), p(rotations), p(cov3Ds_precomp), fr.saved.data_ptr(), fr.saved.numel(), fr.n_entries, p(g_image),
+                    p(g_alpha), p(d_means3D), p(d_means2D), p(d_shs), p(d_col), p(d_opac), p(d_scales), p(d_rots), p(d_cov))
         if ctx.means2D_shape is None or not ctx.needs_input_grad[2]:
             d_means2D = None
         elif ctx.means2D_shape != (n, 3):
             raise RuntimeError(f"means2D: expected shape {(n, 3)} to receive its gradient, got {ctx.means2D_shape}")
         return None, d_means3D, d_means2D, d_opac, d_shs, d_col, d_scales, d_rots, d_cov
-
-
-def _ptr(t):
-    return None if t is None or t.numel() == 0 else t.data_ptr()
 
 
 class GaussianRasterizer:
@@ -223,9 +213,7 @@ class GaussianRasterizer:
         if self._last.last_user is None or self._last.last_user() is not self:
             raise RuntimeError("another rasteriser has rendered on this device and stream since: its counts replaced these")
         st = L.RasterStats()
-        rc = self._last.lib.mpmhip_raster_stats(self._last.ptr, C.byref(st))
-        if rc != L.OK:
-            raise L.MPMHipError(rc, "mpmhip_raster_stats failed")
+        call_handle("mpmhip_raster_stats", self._last.ptr, C.byref(st))
         return {k: int(getattr(st, k)) for k, _ in L.RasterStats._fields_}
 
     def forward(self, means3D, means2D=None, opacities=None, shs=None, colors_precomp=None, scales=None, rotations=None,
@@ -249,11 +237,11 @@ class GaussianRasterizer:
         # means2D requiring grad alone builds no graph: the eval loop passes it so and reads no gradient
         graph = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in given.values())
         with torch.no_grad():
-            m = _chk(means3D.detach(), torch.float32, "means3D")
+            m = expect(means3D.detach(), torch.float32, "means3D")
             if m.dim() != 2 or m.shape[1] != 3:
                 raise RuntimeError(f"means3D: expected shape (n, 3), got {tuple(m.shape)}")
             n, dev = m.shape[0], m.device
-            same = lambda t, name, shape: _chk(t.detach() if isinstance(t, torch.Tensor) else t, torch.float32, name, shape)
+            same = lambda t, name, shape: expect(t.detach() if isinstance(t, torch.Tensor) else t, torch.float32, name, shape=shape)
             op = same(opacities, "opacities", (n, 1)) if opacities.dim() == 2 else same(opacities, "opacities", (n,))
             n_sh, deg = 0, int(s.sh_degree)
             if shs is not None:
@@ -286,14 +274,7 @@ class GaussianRasterizer:
                                   view.data_ptr(), proj.data_ptr(), campos.data_ptr())
             hd = self._handle(dev)
             if not graph:
-                image = torch.empty(3, h, w, dtype=torch.float32, device=dev)
-                alpha = torch.empty(1, h, w, dtype=torch.float32, device=dev)
-                radii = torch.empty(n, dtype=torch.int32, device=dev)
-                p = _ptr
-                rc = hd.lib.mpmhip_raster_forward(hd.ptr, C.byref(cs), n, p(m), p(shs), n_sh, p(colors_precomp), p(op), p(scales),
-                                                  p(rotations), p(cov3Ds_precomp), image.data_ptr(), alpha.data_ptr(), p(radii))
-                if rc != L.OK:
-                    raise L.MPMHipError(rc, "mpmhip_raster_forward failed")
+                image, alpha, radii = _launch_forward(hd, cs, n, n_sh, (m, shs, colors_precomp, op, scales, rotations, cov3Ds_precomp), False)
                 self._last, hd.last_user = hd, weakref.ref(self)
                 return image, None, None, alpha, radii, None
         # the validated values above are detached views of these: the same memory, now with the graph's leaves attached

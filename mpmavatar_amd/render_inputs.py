@@ -25,7 +25,8 @@ from __future__ import annotations
 import torch
 
 from . import _lib as L
-from .mesh_frames import MeshFrames, _Bind, _GaussianTable, _chk, _launch_bind, _wants_grad
+from ._call import expect, wants_grad
+from .mesh_frames import MeshFrames, _Bind, _GaussianTable, _launch_bind
 
 
 class BoundGaussians:
@@ -33,15 +34,15 @@ class BoundGaussians:
     ``_rotation``, ``_scaling``, ``_opacity``, ``_features_dc`` / ``_features_rest`` and ``binding`` (Gaussian -> face)."""
 
     def __init__(self, xyz, rotation, scaling, opacity, features_dc, features_rest, binding):
-        self._xyz, self._rotation, self._scaling = _chk(xyz, torch.float32, "_xyz", 3), _chk(rotation, torch.float32, "_rotation", 4), \
-            _chk(scaling, torch.float32, "_scaling", 3)
-        self._opacity = _chk(opacity, torch.float32, "_opacity", 1)
+        self._xyz, self._rotation, self._scaling = expect(xyz, torch.float32, "_xyz", last=3), \
+            expect(rotation, torch.float32, "_rotation", last=4), expect(scaling, torch.float32, "_scaling", last=3)
+        self._opacity = expect(opacity, torch.float32, "_opacity", last=1)
         self._features_dc, self._features_rest = features_dc, features_rest
-        self.binding = _chk(binding.to(torch.int32).contiguous(), torch.int32, "binding")
+        self.binding = expect(binding.to(torch.int32).contiguous(), torch.int32, "binding")
         n = self.binding.numel()
         if not (self._xyz.shape[0] == self._rotation.shape[0] == self._scaling.shape[0] == self._opacity.shape[0] == n):
             raise RuntimeError("BoundGaussians: parameter tensors must have one row per binding entry")
-        self._lib = L.load()
+        L.load()                                 # a missing library is reported here, not at the first launch
         self._gtable = _GaussianTable()
 
     @property
@@ -59,15 +60,15 @@ class BoundGaussians:
         if extra is not None:
             if override_color is None:
                 raise RuntimeError("extra primitives carry precomputed colours: pass override_color for the bound Gaussians too")
-            ex = [_chk(t.contiguous(), torch.float32, f"extra[{i}]", w) for i, (t, w) in enumerate(zip(extra, (3, 3, 1, 3, 4)))]
+            ex = [expect(t.contiguous(), torch.float32, f"extra[{i}]", last=w) for i, (t, w) in enumerate(zip(extra, (3, 3, 1, 3, 4)))]
             m = ex[0].shape[0]
         fr = (frames.face_center, frames.face_orien_mat, frames.face_orien_quat, frames.face_scaling)
         params, tail = (self._xyz, self._rotation, self._scaling, self._opacity), (ex[0], ex[2], ex[3], ex[4])
         means2D = torch.empty(n + m, 3, dtype=torch.float32, device=dev)     # cleared by the same launch; a fresh leaf, outside the graph
-        if _wants_grad(*params, *fr, *tail):
-            out = _Bind.apply(self._lib, self._gtable, self.binding, True, means2D.data_ptr(), self.binding, *fr, *params, *tail)
+        if wants_grad(*params, *fr, *tail):
+            out = _Bind.apply(self._gtable, self.binding, True, means2D.data_ptr(), self.binding, *fr, *params, *tail)
         else:
-            out = _launch_bind(self._lib, True, means2D.data_ptr(), self.binding, fr, params, tail)
+            out = _launch_bind(True, means2D.data_ptr(), self.binding, fr, params, tail)
         means3D, rots, scales, opac = out
         shs = colors = None
         if override_color is None:

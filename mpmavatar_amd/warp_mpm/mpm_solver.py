@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from .._call import call
 from .mpm_data_structure import MPMModelStruct, MPMStateStruct
 
 _MATERIALS = {"jelly": 0, "metal": 1, "sand": 2, "foam": 3, "snow": 4, "plasticine": 5, "neo-hookean": 6, "cloth": 7}
@@ -408,12 +409,8 @@ class MPMWARP(object):
             raise RuntimeError(f"export_particle_cov_to_torch: the state lives on {Ft.device}, not on {device}")
         new_cov = torch.zeros(n * 6, dtype=torch.float32, device=Ft.device)
         if n:
-            dev = Ft.device
             self.synchronize()   # F_trial was written back on the context's stream; the launch below goes on torch's current stream
-            rc = self._lib.mpmhip_cov_from_F(dev.index or 0, torch.cuda.current_stream(dev).cuda_stream, Ft.data_ptr(),
-                                             cov0.data_ptr(), n, new_cov.data_ptr())
-            if rc != 0:
-                raise RuntimeError(f"mpmhip_cov_from_F failed ({rc})")
+            call("mpmhip_cov_from_F", Ft.device, Ft.data_ptr(), cov0.data_ptr(), n, new_cov.data_ptr())
         return new_cov
 
     # ------------------------------------------------------------------ introspection (not in the reference)

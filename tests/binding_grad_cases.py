@@ -11,12 +11,12 @@ The loss of a case is  sum(w_m * means3D) + sum(w_r * rotations) + sum(w_s * sca
 """
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import torch
 
 import binding_twin_torch as tw
+import hostbuild
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -99,33 +99,15 @@ def csr(keys, n_keys):
 
 # ---- the host build of frames_grad_math.hpp -------------------------------------------------------------------------------------
 
-SRC = os.path.join(HERE, "hostframes_grad", "hostframes_grad.cpp")
-CSRC = os.path.join(ROOT, "mpmavatar_amd", "csrc")
-HDR = os.path.join(CSRC, "frames_grad_math.hpp")
-OUT = os.path.join(HERE, "hostframes_grad", "_build")
-_host = None
-
-
-def _compile(target, extra):
-    os.makedirs(OUT, exist_ok=True)
-    path = os.path.join(OUT, target)
-    if not os.path.exists(path) or os.path.getmtime(path) < max(os.path.getmtime(p) for p in (SRC, HDR)):
-        subprocess.check_call(["g++", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(HERE, "hostmath", "stub"), "-I", CSRC] + extra +
-                              [SRC, "-o", path])
-    return path
-
-
 def host_lib():
-    global _host
-    if _host is None:
-        _host = C.CDLL(_compile("libhostframes_grad.so", ["-O2", "-fPIC", "-shared"]))
-    return _host
+    return hostbuild.host_lib("hostframes_grad")
 
 
 def sanitizer_program():
     """the same file as a stand-alone program under AddressSanitizer and UBSan (run as a subprocess; nothing is loaded into Python)"""
-    return _compile("hostframes_grad_asan", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                                             "-DHOSTFRAMES_GRAD_MAIN"])
+    return hostbuild.host_program("hostframes_grad", name="hostframes_grad_asan",
+                                  flags=["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                                         "-DHOSTFRAMES_GRAD_MAIN"])
 
 
 def _p(a):

@@ -11,9 +11,10 @@ utils/image_utils.py on the CPU, in float64 and in float32); nothing here modifi
 """
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+import hostbuild
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -79,24 +80,11 @@ def d_loss_64(name, lam=LAMBDA):
 
 # ---- the host build of image_loss_math.hpp ------------------------------------------------------------------------------
 
-SRC = os.path.join(HERE, "hostimage", "hostimage.cpp")
-CSRC = os.path.join(ROOT, "mpmavatar_amd", "csrc")
-HDR = os.path.join(CSRC, "image_loss_math.hpp")
-OUT = os.path.join(HERE, "hostimage", "_build")
 fp = C.POINTER(C.c_float)
-_host = None
 
 
 def host_lib():
-    global _host
-    if _host is None:
-        os.makedirs(OUT, exist_ok=True)
-        lib = os.path.join(OUT, "libhostimage.so")
-        if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(p) for p in (SRC, HDR)):
-            subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off", "-I",
-                                   os.path.join(HERE, "hostmath", "stub"), "-I", CSRC, SRC, "-o", lib])
-        _host = C.CDLL(lib)
-    return _host
+    return hostbuild.host_lib("hostimage")
 
 
 def _p(a):

@@ -58,6 +58,8 @@ def test_struct_layouts_match_header():
     assert fields("mpmhip_model_scalars") == [f for f, _ in L.ModelScalars._fields_]
     assert fields("mpmhip_stats") == [f for f, _ in L.Stats._fields_]
     assert fields("mpmhip_dist_peer") == [f for f, _ in L.DistPeer._fields_]
+    assert fields("mpmhip_raster_settings") == [f for f, _ in L.RasterSettings._fields_]
+    assert fields("mpmhip_raster_stats_t") == [f for f, _ in L.RasterStats._fields_]
 
 
 def test_version_and_device_count(lib):
@@ -75,6 +77,41 @@ def test_create_validates_and_never_falls_back_to_cpu(lib):
         assert lib.mpmhip_create(C.byref(ok), C.byref(ctx)) == L.ERR_NO_DEVICE
         assert b"no CPU fallback" in lib.mpmhip_last_error(None)
         assert not ctx.value
+
+
+# the entry points that take (device, stream, ...) instead of a context or a handle
+STATELESS = ("mpmhip_cov_from_F", "mpmhip_face_frames", "mpmhip_bind_gaussians", "mpmhip_render_inputs", "mpmhip_render_inputs_backward",
+             "mpmhip_face_frames_backward", "mpmhip_face_areas", "mpmhip_mesh_sample", "mpmhip_nn_dist2", "mpmhip_geo_reduce",
+             "mpmhip_image_loss_forward", "mpmhip_image_loss_backward")
+ZERO_COUNT_IS_NO_WORK = STATELESS[:6]     # csrc/frames.hip and csrc/frames_backward.hip: a count of 0 is a valid request for nothing
+
+
+def _stateless_args(name, pointer, count):
+    """what follows (device, stream): every pointer `pointer`, every count `count`, tau = 1e-3"""
+    return [count if t is C.c_int32 else 1e-3 if t is C.c_double else pointer for t in L.SIGNATURES[name][1][2:]]
+
+
+def test_stateless_entry_points_check_arguments_then_device_then_empty_work(lib):
+    """The order of DESIGN.md section 10 as return codes: a bad argument is MPMHIP_ERR_INVALID whatever the device, a device that
+    does not exist is MPMHIP_ERR_NO_DEVICE even for a request for nothing.  Every call names device -1, so nothing is launched
+    on any machine; the pointers are the address of a host buffer nothing reads before the return."""
+    buf = C.create_string_buffer(64)
+    p = C.addressof(buf)
+    for name in STATELESS:
+        f = getattr(lib, name)
+        assert f(-1, None, *_stateless_args(name, p, 1)) == L.ERR_NO_DEVICE, name
+        # mpmhip_render_inputs_backward without a single output pointer asks for nothing: valid, so the device decides
+        want = L.ERR_NO_DEVICE if name == "mpmhip_render_inputs_backward" else L.ERR_INVALID
+        assert f(-1, None, *_stateless_args(name, None, 1)) == want, name
+    args = _stateless_args("mpmhip_render_inputs_backward", None, 1)
+    args[2 + 12] = p                                                   # d_xyz wanted, binding missing
+    assert lib.mpmhip_render_inputs_backward(-1, None, *args) == L.ERR_INVALID
+    for name in ZERO_COUNT_IS_NO_WORK:
+        for pointer in (p, None):
+            assert getattr(lib, name)(-1, None, *_stateless_args(name, pointer, 0)) == L.ERR_NO_DEVICE, name
+    h = L.vp()
+    assert lib.mpmhip_raster_create(-1, None, C.byref(h)) == L.ERR_NO_DEVICE and not h.value
+    assert lib.mpmhip_raster_create(-1, None, None) == L.ERR_INVALID
 
 
 def test_shim_refuses_cpu_device(lib):

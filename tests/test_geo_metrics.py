@@ -4,30 +4,20 @@ test_hip_math_on_host.py compiles mpm_math.hpp) against the fixture the referenc
 tests/test_gpu_geo_metrics.py."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import geo_checks as gc
+from hostbuild import host_lib
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SRC = os.path.join(HERE, "hostgeo", "hostgeo.cpp")
-HDR = os.path.join(ROOT, "mpmavatar_amd", "csrc", "geo_math.hpp")
-OUT = os.path.join(HERE, "hostgeo", "_build")
 
 fp, ip, dp = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_double)
 
 
 @pytest.fixture(scope="module")
 def hg():
-    os.makedirs(OUT, exist_ok=True)
-    lib = os.path.join(OUT, "libhostgeo.so")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(SRC), os.path.getmtime(HDR)):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off", "-I",
-                               os.path.join(HERE, "hostmath", "stub"), "-I", os.path.dirname(HDR), SRC, "-o", lib])
-    return C.CDLL(lib)
+    return host_lib("hostgeo")
 
 
 def nn(hg, src, dst):

@@ -17,32 +17,21 @@ discontinuity of the cloth return mapping (mpm_utils.py:196-204): 2.7x further f
 wp.qr3 as the oracle restates it; `test_gram_schmidt_qr_is_the_outlier` keeps that witness.
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import refgolden as rg
+from hostbuild import host_lib
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SRC = os.path.join(HERE, "hostmath", "hostmath.cpp")
-HDR = os.path.join(ROOT, "mpmavatar_amd", "csrc", "mpm_math.hpp")
-OUT = os.path.join(HERE, "hostmath", "_build")
 
 ELEM = C.CFUNCTYPE(None, *([C.POINTER(C.c_float)] * 2 + [C.c_float] * 6 + [C.POINTER(C.c_float)] * 5))
 TRAD = C.CFUNCTYPE(None, C.POINTER(C.c_float), C.c_int, *([C.c_float] * 6 + [C.POINTER(C.c_float)] * 5))
 
 
 def _build(contract):
-    os.makedirs(OUT, exist_ok=True)
-    lib = os.path.join(OUT, f"libhostmath_{contract}.so")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(SRC), os.path.getmtime(HDR)):
-        flags = ["-ffp-contract=off"] if contract == "off" else ["-ffp-contract=fast", "-mfma"]
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-Wno-unknown-pragmas", *flags,
-                               "-I", os.path.join(HERE, "hostmath", "stub"), "-I", os.path.dirname(HDR), SRC, "-o", lib])
-    return C.CDLL(lib)
+    flags = ["-ffp-contract=off"] if contract == "off" else ["-ffp-contract=fast", "-mfma"]
+    return host_lib("hostmath", name=f"hostmath_{contract}", flags=["-Wno-unknown-pragmas", *flags])
 
 
 @pytest.fixture(scope="module")

@@ -3,9 +3,6 @@
 float64 torch twin (tests/raster_twin_torch.py); the measurement of G32, the constant the GPU bound is built on; the conditions
 the committed scenes must meet; torch.autograd.gradcheck of the twin as an anchor independent of our derivation; a known answer."""
 import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
@@ -14,13 +11,7 @@ import raster_grad_scenes as gs
 import raster_scenes as rs
 import raster_twin as tw
 import raster_twin_torch as tt
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SRC = os.path.join(HERE, "hostraster_grad", "hostraster_grad.cpp")
-CSRC = os.path.join(ROOT, "mpmavatar_amd", "csrc")
-HDRS = [os.path.join(CSRC, "raster_grad_math.hpp"), os.path.join(CSRC, "raster_math.hpp")]
-OUT = os.path.join(HERE, "hostraster_grad", "_build")
+from hostbuild import host_lib
 
 fp = C.POINTER(C.c_float)
 IDS = lambda k: "-".join(map(str, k))
@@ -28,12 +19,7 @@ IDS = lambda k: "-".join(map(str, k))
 
 @pytest.fixture(scope="module")
 def hg():
-    os.makedirs(OUT, exist_ok=True)
-    lib = os.path.join(OUT, "libhostraster_grad.so")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(p) for p in [SRC] + HDRS):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off", "-I",
-                               os.path.join(HERE, "hostmath", "stub"), "-I", CSRC, SRC, "-o", lib])
-    so = C.CDLL(lib)
+    so = host_lib("hostraster_grad")
     so.hg_backward.restype = C.c_int64
     return so
 

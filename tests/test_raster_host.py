@@ -12,12 +12,10 @@ import pytest
 
 import raster_scenes as rs
 import raster_twin as tw
+from hostbuild import host_lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SRC = os.path.join(HERE, "hostraster", "hostraster.cpp")
-HDR = os.path.join(ROOT, "mpmavatar_amd", "csrc", "raster_math.hpp")
-OUT = os.path.join(HERE, "hostraster", "_build")
 EPS = 2.0 ** -24
 
 fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
@@ -25,12 +23,7 @@ fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
 
 @pytest.fixture(scope="module")
 def hr():
-    os.makedirs(OUT, exist_ok=True)
-    lib = os.path.join(OUT, "libhostraster.so")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(SRC), os.path.getmtime(HDR)):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off", "-I",
-                               os.path.join(HERE, "hostmath", "stub"), "-I", os.path.dirname(HDR), SRC, "-o", lib])
-    return C.CDLL(lib)
+    return host_lib("hostraster")
 
 
 def _p(a, t=fp):
