@@ -143,7 +143,7 @@ __global__ void k_face_splat(const float *pts, const float *vel, float adv, cons
     for (int j = 0; j < 3; ++j)
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
-        float w = sel3(i, s.w0.x, s.w1.x, s.w2.x) * sel3(j, s.w0.y, s.w1.y, s.w2.y) * sel3(k, s.w0.z, s.w1.z, s.w2.z);
+        float w = stencil_w(s, i, j, k);
         size_t g = gidx(gd.G, s.bx + i, s.by + j, s.bz + k);
         atomicAdd(v_in + 3 * g, w * fv.x); atomicAdd(v_in + 3 * g + 1, w * fv.y); atomicAdd(v_in + 3 * g + 2, w * fv.z);
         atomicAdd(normal + 3 * g, w * fn.x); atomicAdd(normal + 3 * g + 1, w * fn.y); atomicAdd(normal + 3 * g + 2, w * fn.z);
@@ -179,7 +179,7 @@ __global__ void k_mover_splat(const float *x, const float *vel, int n, int off, 
     for (int j = 0; j < 3; ++j)
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
-        float w = sel3(i, s.w0.x, s.w1.x, s.w2.x) * sel3(j, s.w0.y, s.w1.y, s.w2.y) * sel3(k, s.w0.z, s.w1.z, s.w2.z);
+        float w = stencil_w(s, i, j, k);
         size_t g = gidx(gd.G, s.bx + i, s.by + j, s.bz + k);
         atomicAdd(velocity + 3 * g, w * pv.x); atomicAdd(velocity + 3 * g + 1, w * pv.y);
         atomicAdd(velocity + 3 * g + 2, w * pv.z);

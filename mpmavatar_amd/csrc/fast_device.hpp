@@ -336,6 +336,20 @@ __device__ __forceinline__ void raise_face(int *counters, int step_id) {
   counters[CNT_FACE] = 1;
   counters[CNT_PAR0 + 2 * (step_id & 1)] = 1;
 }
+// Progress + drift flag for the host, by one thread of the substep's first launch (k_p2g / k_g2p2g): plain stores into pinned host
+// memory instead of a copy + event every few substeps (on the stream those cost a blit kernel and ~10-20 us of idle queue each).
+// Everything before this launch has completed, so substep step_id - 1 is done and its parity slot of the flags holds every warning
+// it raised (final: the kernels of THIS substep raise the other slot); post it and clear it for substep step_id + 1.
+// One ring entry per launch -- (step_id, a body face left its bin's tile, drift flag) -- and the progress word after it.
+// The host decides at substep s with the entry of substep s - host_lead, whatever the GPU has done since: the re-sort
+// schedule is a function of the simulation, not of host / GPU timing, and a run stays bit-reproducible.
+__device__ __forceinline__ void post_host_flags(const GridPtrs &g) {
+  int *prev = g.counters + CNT_PAR0 + 2 * ((g.step_id - 1) & 1);
+  unsigned v = ((unsigned)g.step_id << 2) | (prev[0] != 0 ? 2u : 0u) | (prev[1] != 0 ? 1u : 0u);
+  prev[0] = 0; prev[1] = 0;
+  __hip_atomic_store(g.host_sig + SIG_RING0 + (g.step_id & (SIG_RING_N - 1)), (int)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(g.host_sig + SIG_PROGRESS, g.step_id, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 
 // One node of the grid stage.  ZERO = true consumes the accumulators (re-zeroes what it read); ZERO = false only reads
 // them (g2p evaluates nodes on the fly while it stages its tile, k_zero_blocks / the zeroing workgroups of the next

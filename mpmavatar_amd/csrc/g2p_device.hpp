@@ -452,13 +452,7 @@ template <int STEPS, bool FX>
 __device__ __forceinline__ void g2p2g_body(const ChunkRec *recs, int n_chunks, const Bufs &b, const VAdj &va, const Dims &d, float rpic,
                                            float dt, const GridPtrs &g, const GridRead &rd, const SplatArgs &sa, const TradParams &tp,
                                            const GridParams &gp, const BCList &bcl, double *tile, int *esc, int &esc_n, float *red) {
-  if (blockIdx.x == 0 && threadIdx.x == 0 && g.host_sig) {  // progress + flags of the substep before (see p2g_body)
-    int *prev = g.counters + CNT_PAR0 + 2 * ((g.step_id - 1) & 1);
-    unsigned v = ((unsigned)g.step_id << 2) | (prev[0] != 0 ? 2u : 0u) | (prev[1] != 0 ? 1u : 0u);
-    prev[0] = 0; prev[1] = 0;
-    __hip_atomic_store(g.host_sig + SIG_RING0 + (g.step_id & (SIG_RING_N - 1)), (int)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(g.host_sig + SIG_PROGRESS, g.step_id, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  if (blockIdx.x == 0 && threadIdx.x == 0 && g.host_sig) post_host_flags(g);  // progress + flags of the substep before
   if ((int)blockIdx.x >= sa.e0 && (int)blockIdx.x < sa.e0 + sa.n_extra) {  // splats of substep n + 1 (into W)
     int e = (int)blockIdx.x - sa.e0;
     if (e < sa.n_fbins) col_splat_wg<3>(tile, sa, e, d, g);

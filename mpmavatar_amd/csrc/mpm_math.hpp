@@ -453,6 +453,10 @@ __device__ __forceinline__ Stencil make_stencil(V3 x, float inv_dx) {
   return s;
 }
 __device__ __forceinline__ float sel3(int i, float a, float b, float c) { return i == 0 ? a : (i == 1 ? b : c); }
+// weight of stencil node (i, j, k), associated as (wx * wy) * wz
+__device__ __forceinline__ float stencil_w(const Stencil &s, int i, int j, int k) {
+  return sel3(i, s.w0.x, s.w1.x, s.w2.x) * sel3(j, s.w0.y, s.w1.y, s.w2.y) * sel3(k, s.w0.z, s.w1.z, s.w2.z);
+}
 // weight of stencil node i (compile-time 0..2) at fractional offset f, and its derivative: the values make_stencil
 // stores, recomputed where a kernel would otherwise keep nine of them in registers for a whole loop nest
 __device__ __forceinline__ float bspline_w(int i, float f) {

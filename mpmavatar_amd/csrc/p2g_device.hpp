@@ -1,96 +1,12 @@
-// p2g_device.hpp -- device side of p2g (p2g_apic_with_stress, mpm_utils.py:484-557): the body-face and joint splats, the chunk tile in
-// packed fixed point, the segmented DPP pre-reduction, scatter / flush and the chunk workgroup (p2g_body).  Kernels: p2g.hip.
+// p2g_device.hpp -- device side of p2g (p2g_apic_with_stress, mpm_utils.py:484-557): the chunk tile in packed fixed point, the
+// segmented DPP pre-reduction, scatter / flush and the chunk workgroup (p2g_body); the body-face and joint splats that ride in its
+// launch are in splat_device.hpp.  Kernels: p2g.hip.
 #pragma once
 #include "fast_device.hpp"
 
 namespace mpm {
 inline namespace fk {
 
-// ------------------------------------------------------------------------------------------------
-// body-face splat (compute_mesh, mpm_solver.py:829-880) and joint splat (:677-788) into active blocks
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool splat_ok(int G, const Stencil &s) {
-  return s.bx >= 0 && s.bx < G - 3 && s.by >= 0 && s.by < G - 3 && s.bz >= 0 && s.bz < G - 3;
-}
-
-// Body-mesh collider (compute_mesh, mpm_solver.py:829-880) with the same LDS-tile structure as p2g.  Faces are
-// binned by grid block at each re-sort (rocPRIM sort of the centroid's block key).  Per substep one wavefront per
-// ACTIVE block takes the faces binned there (lane = face: centroid, mean vertex velocity, unit normal with the
-// caller's mesh advection applied), accumulates weight / weight*velocity / weight*normal into a 7-channel fp64
-// LDS tile with ds_add_f64 and flushes the touched nodes to the block-major collider channels with coalesced
-// atomics.  Faces in blocks outside the active list cannot reach a node that carries mass and are skipped; a
-// face that drifted out of its tile margin since the last re-sort falls back to global atomics.
-// (Tried and dropped: gathering the faces per node block inside the grid stage -- no atomics at all, but the few
-// wavefronts next to the body serialise ~50 faces x 60 dependent instructions each and set the kernel's tail.)
-
-__device__ __forceinline__ V3 face_centroid(const float *pts, const float *vel, float adv, const int32_t *idx, int f,
-                                            V3 &p0, V3 &p1, V3 &p2) {
-  int i0 = idx[3 * f], i1 = idx[3 * f + 1], i2 = idx[3 * f + 2];
-  p0 = mesh_point(pts, vel, adv, i0); p1 = mesh_point(pts, vel, adv, i1); p2 = mesh_point(pts, vel, adv, i2);
-  return v3((p0.x + p1.x + p2.x) / 3.0f, (p0.y + p1.y + p2.y) / 3.0f, (p0.z + p1.z + p2.z) / 3.0f);
-}
-
-// non-empty face bins that lie on the active list (order irrelevant), as self-contained records
-struct FaceBin { int blk, start, cnt, pad; };
-
-// Joint splat (add_velocity_{traditional,verts,faces}, mpm_solver.py:677-788) as ONE launch: 32 lanes per joint
-// particle, lane = stencil node (27 used), so every thread has a single short dependency chain instead of a 27-trip
-// loop of dependent loads.  Group 0: the last n_t traditional particles, group 1: the first n_v vertices, group 2:
-// the first n_f elements (caller-order indices; inv[] maps them to sorted slots).
-struct JointSplatArgs {
-  const float *vel_t, *vel_v, *vel_f;
-  int n_t, n_v, n_f;
-  int off_t, off_v;  // caller-order index of the first particle of group 0 / group 1 (group 2 starts at 0)
-  const int *inv;    // caller order -> sorted slot
-  const int *perm;   // sorted slot -> caller order
-  int t_in_tile;     // 1: group 0 is splatted by the p2g chunks themselves (second tile pass), not by mover_splat_wg
-};
-__device__ __forceinline__ void mover_splat_wg(const Bufs &b, const JointSplatArgs &js, int wg, const Dims &d,
-                                               const GridPtrs &g) {
-  const int *inv = js.inv;
-  int t = wg * PT + (int)threadIdx.x;
-  int q = (t >> 5) + (js.t_in_tile ? js.n_t : 0), nn = t & 31;
-  if (nn >= 27 || q >= js.n_t + js.n_v + js.n_f) return;
-  const float *vel;
-  int orig;
-  if (q < js.n_t) { vel = js.vel_t + 3 * (size_t)q; orig = js.off_t + q; }
-  else if (q < js.n_t + js.n_v) { vel = js.vel_v + 3 * (size_t)(q - js.n_t); orig = js.off_v + (q - js.n_t); }
-  else { vel = js.vel_f + 3 * (size_t)(q - js.n_t - js.n_v); orig = q - js.n_t - js.n_v; }
-  Stencil s = make_stencil(ld3(b.all, A_X, inv[orig]), d.inv_dx);
-  if (!splat_ok(d.G, s)) return;  // mpm_solver.py:692,730,767
-  int i = nn / 9, j = (nn / 3) % 3, k = nn % 3;
-  float w = sel3(i, s.w0.x, s.w1.x, s.w2.x) * sel3(j, s.w0.y, s.w1.y, s.w2.y) * sel3(k, s.w0.z, s.w1.z, s.w2.z);
-  int x = s.bx + i, y = s.by + j, z = s.bz + k;
-  int blk = blk_of(x, y, z, d.NB);
-  if (!g.ab_flag[blk]) { atomicAdd(g.counters + CNT_DROPPED, 1); return; }
-  V3 pv = load_v3(vel);
-  float *p = g.mov + ((size_t)blk * GCH_MOV) * 64 + loc_of(x, y, z);
-  atomicAdd(p, w);
-  atomicAdd(p + 64, w * pv.x); atomicAdd(p + 128, w * pv.y); atomicAdd(p + 192, w * pv.z);
-}
-
-// The two splats are small, latency-bound and independent of the particle transfer, so they ride along in the p2g
-// LAUNCH as extra workgroups (k_p2g: blockIdx < n_extra) instead of being kernels of their own: as separate launches
-// they either sit on the critical path (17 us) or, on a side stream, cost two cross-queue barrier packets per
-// substep (~6 us of idle GPU each, measured with rocprofv3 --kernel-trace).
-struct SplatArgs {
-  const float *pts, *vel;  // body mesh at this substep: pts + adv * vel
-  float adv;
-  const int *fidx;         // [n_f][3] vertex ids in bin order
-  const FaceBin *fbins;
-  int n_fbins;             // workgroups [0, n_fbins): one face bin each
-  int splat_passes;        // 3: both passes of the body-face splat here; 2: only the normal pass (pass 0 rode in the stress launch)
-  JointSplatArgs js;       // workgroups [n_fbins, n_fbins + n_mov_wg): joints
-  int n_mov_wg;
-  int n_extra;             // n_fbins + n_mov_wg rounded up to a multiple of 8 (keeps the XCD mapping of the chunks)
-  int e0;                  // first workgroup of the splats: 0 (in front of the chunks) or xcd_grid(n_chunks) (behind them)
-  ZeroArgs z;              // workgroups [z_first, z_first + z.n_wg), after the chunk workgroups: clear the other
-  int z_first;             // accumulator buffer
-  PackArgs pack;           // workgroups [pack.first, ...) after those: multi-GPU halo pack (see PackArgs)
-};
-
-// PASS 0: weight + weight*velocity (collider channels 0..3), PASS 1: weight*normal (channels 4..6); both passes use
-// the 4-channel fp64 tile of p2g.
 struct P2GParticle {
   Stencil s;
   float mass;
@@ -499,356 +415,14 @@ __device__ __forceinline__ void p2g_flush(double *tile, int ox, int oy, int oz, 
   }
 }
 
-// joint splat of one out-of-margin particle (second tile pass of k_p2g<.., JT = true>)
-__device__ __forceinline__ void mover_escaped(V3 x, V3 pv, const Dims &d, const GridPtrs &g) {
-  Stencil s = make_stencil(x, d.inv_dx);
-#pragma unroll 1
-  for (int n = 0; n < 27; ++n) {
-    int i = n / 9, j = (n / 3) % 3, k = n % 3;
-    float w = sel3(i, s.w0.x, s.w1.x, s.w2.x) * sel3(j, s.w0.y, s.w1.y, s.w2.y) * sel3(k, s.w0.z, s.w1.z, s.w2.z);
-    int gx = s.bx + i, gy = s.by + j, gz = s.bz + k;
-    int blk = blk_of(gx, gy, gz, d.NB);
-    if (!g.ab_flag[blk]) { atomicAdd(g.counters + CNT_DROPPED, 1); continue; }
-    float *p = g.mov + ((size_t)blk * GCH_MOV) * 64 + loc_of(gx, gy, gz);
-    atomicAdd(p, w);
-    atomicAdd(p + 64, w * pv.x); atomicAdd(p + 128, w * pv.y); atomicAdd(p + 192, w * pv.z);
-  }
-}
+}  // namespace fk
+}  // namespace mpm
 
-// Faces are sorted by (block, cell of the centroid) at the re-sort, so neighbouring lanes mostly hold faces of the same
-// cell and add into the same 27 tile nodes: the same segmented DPP pre-reduction as the particle scatter (p2g_scatter)
-// leaves one lane per run issuing the LDS atomics.  DBG 4096 switches the pre-reduction off (every lane issues).
-// Two passes through the four-channel tile per batch of faces -- (weight, weight * velocity), then weight * normal -- with
-// the face, its stencil and the scan masks loaded / computed once for both (seven channels at once would need 43 KB of LDS:
-// three instead of five workgroups per CU for the whole launch).
-template <int PASS>
-__device__ __forceinline__ void col_splat_scatter(double *tile, const Stencil &s, float on, V3 c, SegMask sm, bool do_add, int base) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    float wx = sel3(i, s.w0.x, s.w1.x, s.w2.x) * on;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      float wxy = wx * sel3(j, s.w0.y, s.w1.y, s.w2.y);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        float w = wxy * sel3(k, s.w0.z, s.w1.z, s.w2.z);
-        float r0 = w * c.x, r1 = w * c.y, r2 = w * c.z, r3 = w;
-        seg_scan4<3>(r0, r1, r2, r3, sm);
-        if (do_add) {
-          double *p = tile + base + tile_idx(i, j, k);
-          if (PASS == 0) {
-            atomicAdd(p, (double)r3);
-            atomicAdd(p + TILE_PAD, (double)r0); atomicAdd(p + 2 * TILE_PAD, (double)r1); atomicAdd(p + 3 * TILE_PAD, (double)r2);
-          } else {
-            atomicAdd(p, (double)r0); atomicAdd(p + TILE_PAD, (double)r1); atomicAdd(p + 2 * TILE_PAD, (double)r2);
-          }
-        }
-      }
-    }
-  }
-}
-template <int PASS>
-__device__ __forceinline__ void col_splat_flush(const double *tile, int ox, int oy, int oz, int bx, int by, int bz,
-                                                unsigned long long act_mask, const Dims &d, const GridPtrs &g) {
-  for (int t = threadIdx.x; t < TILE3; t += PT) {
-    int ti = t >> 6, tj = (t >> 3) & 7, tk = t & 7;
-    const double *q = tile + tile_idx(ti, tj, tk);
-    float c0 = (float)q[0], c1 = (float)q[TILE_PAD], c2 = (float)q[2 * TILE_PAD];
-    float c3 = PASS == 0 ? (float)q[3 * TILE_PAD] : 0.0f;
-    if (PASS == 0 ? c0 == 0.0f : (c0 == 0.0f && c1 == 0.0f && c2 == 0.0f)) continue;
-    int x = ox + ti, y = oy + tj, z = oz + tk;
-    if (!in_grid(x, y, z, d.G)) continue;
-    int nb = blk_of(x, y, z, d.NB);
-    int nidx = (((x >> 2) - bx + 1) * 3 + ((y >> 2) - by + 1)) * 3 + ((z >> 2) - bz + 1);
-    if (!((act_mask >> nidx) & 1ull)) continue;  // inactive block: never read by g2p, never re-zeroed
-    float *p = g.col + ((size_t)nb * GCH_COL) * 64 + loc_of(x, y, z) + (PASS == 0 ? 0 : 256);
-    atomicAdd(p, c0); atomicAdd(p + 64, c1); atomicAdd(p + 128, c2);
-    if (PASS == 0) { atomicAdd(p + 192, c3); __hip_atomic_store(&g.col_flag[nb], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-  }
-}
+// the body-face and joint splats: extra workgroups of the p2g launches (uses the DPP pre-reduction above)
+#include "splat_device.hpp"
 
-// One-pass form of the small-bin splat (PASSES == 3): all seven collider channels (weight, weight * velocity, weight * normal) in
-// one tile of 8 x 8 x 8 nodes at strides (67, 8, 1) -- 2 * (67 i + 8 j + k) mod 64 puts 25 of a face's 27 nodes into different bank
-// pairs -- so that a bin costs one clearing, one scatter and one flush instead of two of each with five barriers in between.  The
-// workgroup tile is 7 * 536 doubles = 30 KB instead of 24.6 KB: still five workgroups per CU (VGPR-bound at five).
-constexpr int SPLAT7_SI = 67, SPLAT7_SJ = 8, SPLAT7_S = 536;  // 7*67 + 7*8 + 7 = 532 < 536
-#ifndef SPLAT_ONEPASS
-#define SPLAT_ONEPASS 1  // experiment switch: 0 = small bins take the two-pass path through the four-channel tile (24.6 KB per workgroup)
-#endif
-constexpr int P2G_TILE_DOUBLES = (SPLAT_ONEPASS && 7 * SPLAT7_S > 4 * TILE_PAD) ? 7 * SPLAT7_S : 4 * TILE_PAD;
-constexpr int SPLAT_SMALL = 32;  // faces per bin up to which the splat workgroup maps lanes to (face, node) pairs
-// PASSES: bit 0 = the weight / velocity pass (w, w v_face: collider channels 0-3, sets col_flag), bit 1 = the normal pass (w n:
-// channels 4-6).  3 = both in one workgroup, as rounds 1-3 did.  Round 4: in cloth scenes the two passes ride in DIFFERENT
-// launches -- pass 0 in front of the stress kernel, pass 1 in the p2g launch -- because a two-pass splat workgroup lives 10-17 us and
-// set the length of the p2g launch in scenes that fit one round of workgroups (garment-120k: p2g 18 us for 10 us chunk
-// workgroups), while the stress launch before it has room (9 us of streaming work, no LDS, one round).  Nothing reads the collider
-// channels before g2p; the buffer they go into was cleared by the p2g launch of the substep before.
-template <int PASSES>
-__device__ __forceinline__ void col_splat_wg(double *tile, const SplatArgs &sa, int bin, const Dims &d, const GridPtrs &g) {
-  const FaceBin fb = sa.fbins[bin];
-  int blk = fb.blk;
-  int bz = blk % d.NB, by = (blk / d.NB) % d.NB, bx = blk / (d.NB * d.NB);
-  int ox = 4 * bx - 1, oy = 4 * by - 1, oz = 4 * bz - 1;
-  // active flags of the 27 blocks the tile overlaps (lane n < 27 of every wavefront -> neighbour n)
-  bool nb_act = false;
-  const int l = threadIdx.x;
-  if ((l & 63) < 27) {
-    int n = l & 63;
-    int x = bx + n / 9 - 1, y = by + (n / 3) % 3 - 1, z = bz + n % 3 - 1;
-    if ((unsigned)x < (unsigned)d.NB && (unsigned)y < (unsigned)d.NB && (unsigned)z < (unsigned)d.NB)
-      nb_act = g.ab_flag[(x * d.NB + y) * d.NB + z] != 0;
-  }
-  // (the one-pass path takes the ballot -- i.e. the wait for the flags -- right before its flush: in front of the tile clearing it was
-  // one more dependent memory level at the head of the workgroup)
-  const bool one_pass = PASSES == 3 && SPLAT_ONEPASS && fb.cnt <= SPLAT_SMALL;
-  unsigned long long act_mask = one_pass ? 0ull : __ballot(nb_act);
-  const int end = fb.start + fb.cnt;
-  if (fb.cnt <= SPLAT_SMALL) {
-    // SMALL BIN (the common case once the cloth has draped: ~740 bins of ~27 faces): lane = (face, stencil node), 8 faces x 32
-    // lanes (27 used) per step, <= 4 steps -- instead of lane = face with a 27-trip node loop of dependent DPP scans that 230
-    // of the 256 lanes sit out.  Such a workgroup used to live 10-17 us (two 3 us scatter passes, profiles/r03_wg_timeline.md);
-    // what is left is its chain of loads and the two flushes.  The per-step weights and normals stay in registers for the
-    // second (normal) pass through the four-channel tile.
-    const int fi = l >> 5, n = l & 31;
-    const int ni = n / 9, nj = (n / 3) % 3, nk = n % 3;
-    if (PASSES == 3 && SPLAT_ONEPASS) {  // one pass through a seven-channel tile (see SPLAT7_S)
-      // the first pair's face indices are requested together with the block flags, BEFORE the tile is cleared: behind the barrier they
-      // were a memory level of their own (record -> flags -> [clear, barrier] -> indices -> vertices; now record -> flags + indices -> vertices)
-      int pre_i[2][3];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int q = u * 8 + fi;
-        const int jq = q < fb.cnt ? fb.start + q : fb.start;
-        pre_i[u][0] = sa.fidx[3 * jq]; pre_i[u][1] = sa.fidx[3 * jq + 1]; pre_i[u][2] = sa.fidx[3 * jq + 2];
-      }
-      for (int t = l; t < 7 * SPLAT7_S; t += PT) tile[t] = 0.0;
-      __syncthreads();
-      WGT(g, 0, 2);  // (debug build: bin record, block flags, tile cleared)
-      // Two steps' loads in flight at a time, then their LDS atomics; the global atomics of the out-of-margin lanes wait until all
-      // steps are through.  With those inside the load loop (they may alias the vertex arrays) the compiler kept the four steps in
-      // order and a bin paid index -> vertex latency four times: 5.3 us of the workgroup's 11 (profiles/r04_experiments.md 15); all
-      // four steps' loads at once are 84 registers of raw vertex data and cost the whole kernel a wavefront per SIMD.
-      auto face_eval = [&](int it, float &w, V3 &a, V3 &fn, Stencil &s, bool pre = false) -> bool {
-        const int q = it * 8 + fi;
-        const bool have = q < fb.cnt && n < 27;
-        const int jq = q < fb.cnt ? fb.start + q : fb.start;
-        int i0, i1, i2;
-        if (pre) { i0 = pre_i[it & 1][0]; i1 = pre_i[it & 1][1]; i2 = pre_i[it & 1][2]; }  // (it < 2 only)
-        else { i0 = sa.fidx[3 * jq]; i1 = sa.fidx[3 * jq + 1]; i2 = sa.fidx[3 * jq + 2]; }
-        V3 p0 = mesh_point(sa.pts, sa.vel, sa.adv, i0), p1 = mesh_point(sa.pts, sa.vel, sa.adv, i1), p2 = mesh_point(sa.pts, sa.vel, sa.adv, i2);
-        V3 u0 = load_v3(sa.vel + 3 * i0), u1 = load_v3(sa.vel + 3 * i1), u2 = load_v3(sa.vel + 3 * i2);
-        V3 fp = v3((p0.x + p1.x + p2.x) / 3.0f, (p0.y + p1.y + p2.y) / 3.0f, (p0.z + p1.z + p2.z) / 3.0f);
-        a = v3((u0.x + u1.x + u2.x) / 3.0f, (u0.y + u1.y + u2.y) / 3.0f, (u0.z + u1.z + u2.z) / 3.0f);
-        fn = normalize(cross(p1 - p0, p2 - p0));  // wp.mesh_eval_face_normal
-        s = make_stencil(fp, d.inv_dx);
-        w = sel3(ni, s.w0.x, s.w1.x, s.w2.x) * sel3(nj, s.w0.y, s.w1.y, s.w2.y) * sel3(nk, s.w0.z, s.w1.z, s.w2.z);
-        return have && splat_ok(d.G, s);  // mpm_solver.py:858
-      };
-      unsigned esc_mask = 0;  // steps whose face left the tile margin since the faces were binned
-#pragma unroll
-      for (int h = 0; h < SPLAT_SMALL / 8; h += 2) {
-        if (h * 8 >= fb.cnt) break;  // (workgroup-uniform: a bin of at most 16 faces -- the average is 13 -- is done after the first pair)
-        float w[2];
-        V3 a[2], fn[2];
-        int off[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          Stencil s;
-          const bool ok = face_eval(h + u, w[u], a[u], fn[u], s, h == 0);
-          const int lx = s.bx - ox, ly = s.by - oy, lz = s.bz - oz;
-          const bool in_tile = !((unsigned)lx > 5u || (unsigned)ly > 5u || (unsigned)lz > 5u);
-          off[u] = (ok && in_tile) ? (lx + ni) * SPLAT7_SI + (ly + nj) * SPLAT7_SJ + (lz + nk) : -1;
-          if (ok && !in_tile) esc_mask |= 1u << (h + u);
-        }
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-          if (off[u] >= 0) {
-            double *p = tile + off[u];
-            atomicAdd(p, (double)w[u]);
-            atomicAdd(p + SPLAT7_S, (double)(w[u] * a[u].x)); atomicAdd(p + 2 * SPLAT7_S, (double)(w[u] * a[u].y));
-            atomicAdd(p + 3 * SPLAT7_S, (double)(w[u] * a[u].z));
-            atomicAdd(p + 4 * SPLAT7_S, (double)(w[u] * fn[u].x)); atomicAdd(p + 5 * SPLAT7_S, (double)(w[u] * fn[u].y));
-            atomicAdd(p + 6 * SPLAT7_S, (double)(w[u] * fn[u].z));
-          }
-        asm volatile("" : "+v"(esc_mask)::"memory");  // (the next pair's loads stay behind this pair's)
-      }
-      if (esc_mask) {  // rare: this lane's node through global atomics; the flag makes the next re-sort bin the faces again
-        raise_drift(g.counters, g.step_id);
-        raise_face(g.counters, g.step_id);
-#pragma unroll 1
-        for (int it = 0; it < SPLAT_SMALL / 8; ++it) {
-          if (!((esc_mask >> it) & 1u)) continue;
-          float w;
-          V3 a, fn;
-          Stencil s;
-          (void)face_eval(it, w, a, fn, s);
-          int x = s.bx + ni, y = s.by + nj, z = s.bz + nk;
-          int nb = blk_of(x, y, z, d.NB);
-          if (g.ab_flag[nb]) {
-            float *p = g.col + ((size_t)nb * GCH_COL) * 64 + loc_of(x, y, z);
-            __hip_atomic_store(&g.col_flag[nb], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            atomicAdd(p, w);
-            atomicAdd(p + 64, w * a.x); atomicAdd(p + 128, w * a.y); atomicAdd(p + 192, w * a.z);
-            atomicAdd(p + 256, w * fn.x); atomicAdd(p + 320, w * fn.y); atomicAdd(p + 384, w * fn.z);
-          }
-        }
-      }
-      WGT(g, 0, 3);  // faces loaded, LDS atomics of wavefront 0 out
-      act_mask = __ballot(nb_act);
-      __syncthreads();
-      WGT(g, 0, 4);
-      for (int t = l; t < TILE3; t += PT) {  // (same rules as col_splat_flush<0> and <1>: a node without weight got nothing at all)
-        int ti = t >> 6, tj = (t >> 3) & 7, tk = t & 7;
-        const double *q = tile + (ti * SPLAT7_SI + tj * SPLAT7_SJ + tk);
-        float c0 = (float)q[0];
-        if (c0 == 0.0f) continue;
-        int x = ox + ti, y = oy + tj, z = oz + tk;
-        if (!in_grid(x, y, z, d.G)) continue;
-        int nb = blk_of(x, y, z, d.NB);
-        int nidx = (((x >> 2) - bx + 1) * 3 + ((y >> 2) - by + 1)) * 3 + ((z >> 2) - bz + 1);
-        if (!((act_mask >> nidx) & 1ull)) continue;  // inactive block: never read by g2p, never re-zeroed
-        float *p = g.col + ((size_t)nb * GCH_COL) * 64 + loc_of(x, y, z);
-        atomicAdd(p, c0);
-        atomicAdd(p + 64, (float)q[SPLAT7_S]); atomicAdd(p + 128, (float)q[2 * SPLAT7_S]); atomicAdd(p + 192, (float)q[3 * SPLAT7_S]);
-        atomicAdd(p + 256, (float)q[4 * SPLAT7_S]); atomicAdd(p + 320, (float)q[5 * SPLAT7_S]); atomicAdd(p + 384, (float)q[6 * SPLAT7_S]);
-        __hip_atomic_store(&g.col_flag[nb], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      return;
-    }
-    float wk[SPLAT_SMALL / 8];
-    V3 fnk[SPLAT_SMALL / 8];
-    int basek[SPLAT_SMALL / 8];
-    for (int t = l; t < 4 * TILE_PAD; t += PT) tile[t] = 0.0;
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < SPLAT_SMALL / 8; ++it) {
-      wk[it] = 0.0f; fnk[it] = v3(0, 0, 0); basek[it] = 0;
-      if (it * 8 >= fb.cnt) continue;  // (workgroup-uniform: no face left for this step)
-      const int q = it * 8 + fi;
-      const bool have = q < fb.cnt && n < 27;
-      const int jq = q < fb.cnt ? fb.start + q : fb.start;
-      int i0 = sa.fidx[3 * jq], i1 = sa.fidx[3 * jq + 1], i2 = sa.fidx[3 * jq + 2];
-      V3 p0 = mesh_point(sa.pts, sa.vel, sa.adv, i0), p1 = mesh_point(sa.pts, sa.vel, sa.adv, i1), p2 = mesh_point(sa.pts, sa.vel, sa.adv, i2);
-      V3 u0 = load_v3(sa.vel + 3 * i0), u1 = load_v3(sa.vel + 3 * i1), u2 = load_v3(sa.vel + 3 * i2);
-      V3 fp = v3((p0.x + p1.x + p2.x) / 3.0f, (p0.y + p1.y + p2.y) / 3.0f, (p0.z + p1.z + p2.z) / 3.0f);
-      V3 a = v3((u0.x + u1.x + u2.x) / 3.0f, (u0.y + u1.y + u2.y) / 3.0f, (u0.z + u1.z + u2.z) / 3.0f);
-      V3 fn = normalize(cross(p1 - p0, p2 - p0));  // wp.mesh_eval_face_normal
-      Stencil s = make_stencil(fp, d.inv_dx);
-      const bool ok = have && splat_ok(d.G, s);  // mpm_solver.py:858
-      const int lx = s.bx - ox, ly = s.by - oy, lz = s.bz - oz;
-      const bool in_tile = !((unsigned)lx > 5u || (unsigned)ly > 5u || (unsigned)lz > 5u);
-      const float w = sel3(ni, s.w0.x, s.w1.x, s.w2.x) * sel3(nj, s.w0.y, s.w1.y, s.w2.y) * sel3(nk, s.w0.z, s.w1.z, s.w2.z);
-      wk[it] = 0.0f; fnk[it] = fn; basek[it] = 0;
-      if (ok && in_tile) {
-        wk[it] = w;
-        basek[it] = tile_idx(lx + ni, ly + nj, lz + nk);
-        if (PASSES & 1) {
-          double *p = tile + basek[it];
-          atomicAdd(p, (double)w);
-          atomicAdd(p + TILE_PAD, (double)(w * a.x)); atomicAdd(p + 2 * TILE_PAD, (double)(w * a.y)); atomicAdd(p + 3 * TILE_PAD, (double)(w * a.z));
-        }
-      } else if (ok) {  // drifted out of the tile margin since the faces were binned: this lane's node through global atomics
-        raise_drift(g.counters, g.step_id);
-        raise_face(g.counters, g.step_id);
-        int x = s.bx + ni, y = s.by + nj, z = s.bz + nk;
-        int nb = blk_of(x, y, z, d.NB);
-        if (g.ab_flag[nb]) {
-          float *p = g.col + ((size_t)nb * GCH_COL) * 64 + loc_of(x, y, z);
-          if (PASSES & 1) {
-            __hip_atomic_store(&g.col_flag[nb], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            atomicAdd(p, w);
-            atomicAdd(p + 64, w * a.x); atomicAdd(p + 128, w * a.y); atomicAdd(p + 192, w * a.z);
-          }
-          if (PASSES & 2) { atomicAdd(p + 256, w * fn.x); atomicAdd(p + 320, w * fn.y); atomicAdd(p + 384, w * fn.z); }
-        }
-      }
-    }
-    if (PASSES & 1) {
-      __syncthreads();
-      col_splat_flush<0>(tile, ox, oy, oz, bx, by, bz, act_mask, d, g);
-    }
-    if (!(PASSES & 2)) return;
-    if (PASSES & 1) {
-      __syncthreads();
-      for (int t = l; t < 3 * TILE_PAD; t += PT) tile[t] = 0.0;
-      __syncthreads();
-    }
-#pragma unroll
-    for (int it = 0; it < SPLAT_SMALL / 8; ++it)
-      if (wk[it] != 0.0f) {
-        double *p = tile + basek[it];
-        atomicAdd(p, (double)(wk[it] * fnk[it].x)); atomicAdd(p + TILE_PAD, (double)(wk[it] * fnk[it].y));
-        atomicAdd(p + 2 * TILE_PAD, (double)(wk[it] * fnk[it].z));
-      }
-    __syncthreads();
-    col_splat_flush<1>(tile, ox, oy, oz, bx, by, bz, act_mask, d, g);
-    return;
-  }
-  for (int j0 = fb.start; j0 < end; j0 += PT) {  // workgroup-uniform trip count: barriers and DPP need converged lanes
-    for (int t = l; t < 4 * TILE_PAD; t += PT) tile[t] = 0.0;
-    int jj = j0 + l;
-    bool have = jj < end;
-    int jq = have ? jj : fb.start;
-    int i0 = sa.fidx[3 * jq], i1 = sa.fidx[3 * jq + 1], i2 = sa.fidx[3 * jq + 2];
-    V3 p0 = mesh_point(sa.pts, sa.vel, sa.adv, i0), p1 = mesh_point(sa.pts, sa.vel, sa.adv, i1), p2 = mesh_point(sa.pts, sa.vel, sa.adv, i2);
-    V3 u0 = load_v3(sa.vel + 3 * i0), u1 = load_v3(sa.vel + 3 * i1), u2 = load_v3(sa.vel + 3 * i2);
-    V3 fp = v3((p0.x + p1.x + p2.x) / 3.0f, (p0.y + p1.y + p2.y) / 3.0f, (p0.z + p1.z + p2.z) / 3.0f);
-    V3 a = v3((u0.x + u1.x + u2.x) / 3.0f, (u0.y + u1.y + u2.y) / 3.0f, (u0.z + u1.z + u2.z) / 3.0f);
-    V3 fn = normalize(cross(p1 - p0, p2 - p0));  // wp.mesh_eval_face_normal
-    Stencil s = make_stencil(fp, d.inv_dx);
-    bool ok = have && splat_ok(d.G, s);  // mpm_solver.py:858
-    int lx = s.bx - ox, ly = s.by - oy, lz = s.bz - oz;
-    bool in_tile = !((unsigned)lx > 5u || (unsigned)ly > 5u || (unsigned)lz > 5u);
-    bool tile_ok = ok && in_tile;
-    // lanes without a face in the tile carry a unique key (never merged, never issue) and a zero contribution
-    int key = tile_ok ? (lx * TILE + ly) * TILE + lz : -2 - (l & 63);
-    int base = tile_ok ? tile_idx(lx, ly, lz) : 0;
-    float on = tile_ok ? 1.0f : 0.0f;
-    bool any = __any(tile_ok);
-    SegMask sm = seg_masks(key);
-    unsigned long long tails = __ballot(sm.tail);
-    int dist = __ffsll((unsigned long long)(tails >> (l & 63))) - 1;
-    bool do_add = tile_ok && (dist & 7) == 0;
-    if (DBG(g, 4096)) { sm.m1 = sm.m2 = sm.m4 = sm.m8 = 0.0f; do_add = tile_ok; }
-    __syncthreads();
-    if (any && (PASSES & 1)) col_splat_scatter<0>(tile, s, on, a, sm, do_add, base);
-    if (ok && !in_tile) {  // drifted out of the tile margin since the faces were binned
-      raise_drift(g.counters, g.step_id);
-      raise_face(g.counters, g.step_id);  // ... which is what makes the next re-sort bin the faces again (rebin)
-#pragma unroll 1
-      for (int n = 0; n < 27; ++n) {
-        int i = n / 9, j = (n / 3) % 3, k = n % 3;
-        float w = sel3(i, s.w0.x, s.w1.x, s.w2.x) * sel3(j, s.w0.y, s.w1.y, s.w2.y) * sel3(k, s.w0.z, s.w1.z, s.w2.z);
-        int x = s.bx + i, y = s.by + j, z = s.bz + k;
-        int nb = blk_of(x, y, z, d.NB);
-        if (g.ab_flag[nb]) {
-          float *p = g.col + ((size_t)nb * GCH_COL) * 64 + loc_of(x, y, z);
-          if (PASSES & 1) {
-            __hip_atomic_store(&g.col_flag[nb], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            atomicAdd(p, w);
-            atomicAdd(p + 64, w * a.x); atomicAdd(p + 128, w * a.y); atomicAdd(p + 192, w * a.z);
-          }
-          if (PASSES & 2) { atomicAdd(p + 256, w * fn.x); atomicAdd(p + 320, w * fn.y); atomicAdd(p + 384, w * fn.z); }
-        }
-      }
-    }
-    if (PASSES & 1) {
-      __syncthreads();
-      col_splat_flush<0>(tile, ox, oy, oz, bx, by, bz, act_mask, d, g);
-    }
-    if (PASSES == 3) {
-      __syncthreads();
-      for (int t = l; t < 3 * TILE_PAD; t += PT) tile[t] = 0.0;
-    }
-    if (PASSES & 2) {
-      __syncthreads();
-      if (any) col_splat_scatter<1>(tile, s, on, fn, sm, do_add, base);
-      __syncthreads();
-      col_splat_flush<1>(tile, ox, oy, oz, bx, by, bz, act_mask, d, g);
-    }
-    __syncthreads();
-  }
-}
+namespace mpm {
+inline namespace fk {
 
 // JT = true: the mover holds MANY traditional particles (run_demo.py keeps 100k sand particles frozen for the first
 // frames); their joint splat (weight, weight * joint velocity into the mover channels, mpm_solver.py:677-704) is a
@@ -858,20 +432,7 @@ __device__ __forceinline__ void p2g_body(const ChunkRec *recs, int n_chunks, con
                                          float dt, const GridPtrs &g, const SplatArgs &sa, const TradParams &tp, double *tile, int *esc,
                                          int &esc_n, float *red, int bid) {
   WGT(g, 0, 0);
-  if (bid == 0 && threadIdx.x == 0 && g.host_sig) {
-    // progress + drift flag for the host (plain stores into pinned host memory instead of a copy + event every few
-    // substeps: on the stream those cost a blit kernel and ~10-20 us of idle queue each).  Everything before this launch
-    // has completed, so substep step_id - 1 is done and its parity slot of the flags holds every warning it raised (final: the
-    // kernels of THIS substep raise the other slot); post it and clear it for substep step_id + 1.
-    // One ring entry per launch -- (step_id, a body face left its bin's tile, drift flag) -- and the progress word after it.
-    // The host decides at substep s with the entry of substep s - host_lead, whatever the GPU has done since: the re-sort
-    // schedule is a function of the simulation, not of host / GPU timing, and a run stays bit-reproducible.
-    int *prev = g.counters + CNT_PAR0 + 2 * ((g.step_id - 1) & 1);
-    unsigned v = ((unsigned)g.step_id << 2) | (prev[0] != 0 ? 2u : 0u) | (prev[1] != 0 ? 1u : 0u);
-    prev[0] = 0; prev[1] = 0;
-    __hip_atomic_store(g.host_sig + SIG_RING0 + (g.step_id & (SIG_RING_N - 1)), (int)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(g.host_sig + SIG_PROGRESS, g.step_id, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  if (bid == 0 && threadIdx.x == 0 && g.host_sig) post_host_flags(g);
   // The splat workgroups go in front of the chunks (e0 = 0: the longest workgroups of the launch start first) or behind them
   // (e0 = xcd_grid(n_chunks), MPMHIP_SPLAT_FIRST_MAX): measured the same to 1 % early and in the draped state, where ~740 of them
   // take more than half of the first-round slots -- the dispatcher evens it out.

@@ -436,10 +436,12 @@ __global__ void k_face_keys(const float *pts, const float *vel, float adv, const
                             unsigned *keys, int *iota) {
   int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= n_f) return;
+  int i0, i1, i2;
+  load_face(idx, f, i0, i1, i2);
   V3 p0, p1, p2;
-  V3 fp = face_centroid(pts, vel, adv, idx, f, p0, p1, p2);
+  V3 fp = face_centroid(pts, vel, adv, i0, i1, i2, p0, p1, p2);
   // block in the high bits, cell of the block in the low six: faces of one cell end up in neighbouring lanes of the
-  // splat workgroup, which pre-reduces runs of equal cells across lanes (col_splat_pass)
+  // splat workgroup, which pre-reduces runs of equal cells across lanes (col_splat_large)
   int bx = min(max((int)(fp.x * d.inv_dx - 0.5f), 0), d.G - 1), by = min(max((int)(fp.y * d.inv_dx - 0.5f), 0), d.G - 1),
       bz = min(max((int)(fp.z * d.inv_dx - 0.5f), 0), d.G - 1);
   keys[f] = ((unsigned)blk_of(bx, by, bz, d.NB) << 6) | (unsigned)loc_of(bx, by, bz);

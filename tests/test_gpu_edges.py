@@ -303,3 +303,47 @@ def test_body_face_splat_layouts(subdiv, split, oracle_lib, monkeypatch):
     assert np.abs(v - o.v).max() < 2e-4 * max(np.abs(o.v).max(), 0.1)
     moved = np.abs(o.v[:, 1] + 9.8 * 60 * sc.dt) > 1e-3     # particles the sphere has slowed down: the collider is felt
     assert moved.sum() > 50
+
+
+@pytest.mark.parametrize("subdiv", [2, 4])
+@pytest.mark.parametrize("split", ["0", "1"])
+def test_body_faces_that_left_their_bins(subdiv, split, oracle_lib, monkeypatch):
+    """The escape path of the body-face splat, in the four forms of test_body_face_splat_layouts: sheet and body co-move 1.7 cells
+    along +x over the run, so with the re-sort switched off (rebin_interval < 0: faces binned once) faces end outside the tile
+    margin of their bin (base cell in [4b - 1, 4b + 4] per axis: 56 of 320 faces at subdiv 2, 694 of 5,120 at subdiv 4) and add
+    their nodes with global atomics.  CNT_FACE (debug counter 5) is raised by that path alone and stays set until a face sort.
+    Bounds: those of the sheet case of test_out_of_margin_paths."""
+    import ctypes
+    from oracle.scene_adapter import oracle_from_scene, run_scene
+    monkeypatch.setenv("MPMHIP_SPLIT_SPLAT", split)
+    n = 60
+
+    def make():
+        sc = scenes.sheet(n=40, n_grid=48, collider_subdiv=subdiv, span=(0.6, 1.4), y=1.215, name=f"escape-{subdiv}")
+        sc.dt = 1e-4
+        u = np.array([1.7 * sc.grid_lim / sc.n_grid / (n * sc.dt), 0.0, 0.0], np.float32)   # 11.8 m/s
+        sc.v = (sc.v + u).astype(np.float32)
+        sc.mesh_v = np.tile(u, (sc.mesh_vertices.shape[0], 1))
+        return sc
+
+    sc = make()
+    o = oracle_from_scene(sc)
+    run_scene(o, sc, n)
+    res = {}
+    for ri in (-1000000, 0):
+        sim = harness.build_solver(make(), "cuda:0", mode="fast", rebin_interval=ri)
+        harness.run(sim, n, fused=True)
+        face = ctypes.c_int64()
+        sim.solver._call("mpmhip_debug_counter", 5, ctypes.byref(face))
+        res[ri] = (sim.state.particle_x.detach().cpu().numpy(), sim.state.particle_v.detach().cpu().numpy(),
+                   sim.solver.stats(), face.value)
+    xa, va, sta, face_a = res[-1000000]
+    xb, _, stb, _ = res[0]
+    print(f"rebins A {sta['rebins']} B {stb['rebins']} CNT_FACE {face_a} x_A/oracle {rel(xa, o.x):.3g} v_A/oracle {rel(va, o.v):.3g} "
+          f"x_A/x_B {rel(xa, xb):.3g} felt {int((np.abs(o.v[:, 1] + 9.8 * n * sc.dt) > 1e-3).sum())}")
+    assert sta["rebins"] == 1 and stb["rebins"] >= 2
+    assert face_a == 1, "no body face took the escape path"
+    assert rel(xa, o.x) < 1e-3
+    assert rel(va, o.v) < 1e-2
+    assert rel(xa, xb) < 2e-4
+    assert (np.abs(o.v[:, 1] + 9.8 * n * sc.dt) > 1e-3).sum() > 50     # the collider is felt
