@@ -9,11 +9,14 @@
                loss.backward()                              -> image loss, rasteriser, binding and face-frame backward kernels
                optimizer.step()                             (torch.optim.Adam, as the reference)
 
-    python examples/appearance_step_demo.py [--steps 30] [--size 64]
+    python examples/appearance_step_demo.py [--steps 30] [--size 64] [--colors]
 
 The mesh is a 320-face icosphere with two Gaussians per face.  The target image is rendered from perturbed parameters and perturbed
 vertices; Adam then moves ``_xyz``, ``_rotation``, ``_scaling``, ``_opacity`` and a per-vertex ``verts_offset`` towards it, and the
-loss it prints falls.  Colours are fixed (``override_color``): ``convert_SH`` and the shadow network stay in torch in the reference too.
+loss it prints falls.  Without ``--colors`` the colours are fixed (``override_color``).  With it they are the reference's
+``shadow * convert_SH(...)`` (train_appearance.py:120-123) in one more launch, ``gaussians.shaded_colors`` -> mpmhip_shade_colors:
+degree-1 SH features and an 8 x 8 shadow map (a leaf standing in for the output of the shadow network, which stays the caller's
+torch module) are leaves too, and the target is rendered from perturbed ones.
 """
 import argparse
 import os
@@ -28,14 +31,16 @@ from mpmavatar_amd.image_loss import image_loss  # noqa: E402
 from mpmavatar_amd.mesh_frames import MeshFrames  # noqa: E402
 from mpmavatar_amd.rasterizer import GaussianRasterizationSettings, GaussianRasterizer, look_at_camera  # noqa: E402
 from mpmavatar_amd.render_inputs import BoundGaussians  # noqa: E402
+from mpmavatar_amd.shading import ShadowSampler  # noqa: E402
 
 PER_FACE = 2
+SH_DEGREE, MAP_SIZE = 1, 8
 
 
 class Scene:
-    """Everything one training step needs; ``params`` are the five leaves the optimiser moves."""
+    """Everything one training step needs; ``params`` are the five leaves the optimiser moves (eight with ``colors``)."""
 
-    def __init__(self, size=64, device="cuda:0", seed=0, eye=(0.0, 0.3, -2.0)):
+    def __init__(self, size=64, device="cuda:0", seed=0, eye=(0.0, 0.3, -2.0), colors=False):
         dev = torch.device(device)
         g = torch.Generator(device="cpu").manual_seed(seed)
         rnd = lambda *s: torch.randn(*s, generator=g)
@@ -57,20 +62,41 @@ class Scene:
         self.settings = GaussianRasterizationSettings(image_height=size, image_width=size, tanfovx=tanfov, tanfovy=tanfov,
                                                       bg=torch.ones(3, device=dev), scale_modifier=1.0, viewmatrix=view, projmatrix=proj,
                                                       sh_degree=0, campos=campos, prefiltered=False, debug=False)
-        no_sh = (torch.zeros(n, 1, 3, device=dev), torch.zeros(n, 0, 3, device=dev))
+        sh_true = sh_start = (torch.zeros(n, 1, 3, device=dev), torch.zeros(n, 0, 3, device=dev))
+        self.campos, self.sampler, self.shadow_map = campos, None, None
+        if colors:
+            # the colour by direction as the DC term (colour = C0 dc + 0.5), a little view dependence, and a shadow that darkens one side;
+            # each face samples the map at the direction of its centre
+            k = (SH_DEGREE + 1) ** 2
+            dc = ((self.colors - 0.5) / 0.28209479177387814).cpu()[:, None, :]
+            sh_true = (dc.to(dev).contiguous(), (0.1 * rnd(n, k - 1, 3)).to(dev))
+            sh_start = ((dc + 0.5 * rnd(n, 1, 3)).to(dev).contiguous(), torch.zeros(n, k - 1, 3, device=dev))
+            face_centre = self.verts_orig[self.frames.faces.long()].mean(1)
+            self.sampler = ShadowSampler((face_centre / face_centre.norm(dim=1, keepdim=True))[:, :2].contiguous(), MAP_SIZE, MAP_SIZE)
+            ramp = torch.linspace(0.4, 1.0, MAP_SIZE)
+            map_true, map_start = (ramp[None, :] * torch.ones(MAP_SIZE, 1)).to(dev), torch.full((MAP_SIZE, MAP_SIZE), 0.8, device=dev)
         with torch.no_grad():
             self.verts_offset = true_offset.to(dev)
-            self.gaussians = BoundGaussians(*[true[k].to(dev).contiguous() for k in ("_xyz", "_rotation", "_scaling", "_opacity")], *no_sh, binding)
+            self.gaussians = BoundGaussians(*[true[k].to(dev).contiguous() for k in ("_xyz", "_rotation", "_scaling", "_opacity")], *sh_true, binding)
+            if colors:
+                self.shadow_map = map_true
             self.target = self.render()[0]
         self.verts_offset = torch.nn.Parameter(torch.zeros_like(self.verts_orig))
         leaves = [torch.nn.Parameter(start[k].to(dev).contiguous()) for k in ("_xyz", "_rotation", "_scaling", "_opacity")]
-        self.gaussians = BoundGaussians(*leaves, *no_sh, binding)
         self.params = dict(zip(("_xyz", "_rotation", "_scaling", "_opacity"), leaves), verts_offset=self.verts_offset)
+        if colors:
+            sh_start = tuple(torch.nn.Parameter(t) for t in sh_start)
+            self.shadow_map = torch.nn.Parameter(map_start)
+            self.params.update(_features_dc=sh_start[0], _features_rest=sh_start[1], shadow_map=self.shadow_map)
+        self.gaussians = BoundGaussians(*leaves, *sh_start, binding)
 
     def render(self):
         """-> (image [3, size, size], radii [n]) from the current parameters"""
         self.frames.set_mesh_by_verts(self.verts_orig + self.verts_offset)
         args = self.gaussians.render_inputs(self.frames, override_color=self.colors)
+        if self.sampler is not None:             # train_appearance.py:120-123: the colours of this step, from this step's means3D
+            args["colors_precomp"] = self.gaussians.shaded_colors(args["means3D"], self.campos, SH_DEGREE, shadow_map=self.shadow_map,
+                                                                  sampler=self.sampler)
         image, _, _, _, radii, _ = GaussianRasterizer(raster_settings=self.settings)(**args)
         return image, radii
 
@@ -84,9 +110,11 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--size", type=int, default=64)
+    ap.add_argument("--colors", action="store_true", help="train SH features and a shadow map too (mpmhip_shade_colors)")
     a = ap.parse_args(argv)
-    sc = Scene(a.size)
-    lr = {"_xyz": 5e-3, "_rotation": 1e-2, "_scaling": 1e-2, "_opacity": 2e-2, "verts_offset": 1e-3}
+    sc = Scene(a.size, colors=a.colors)
+    lr = {"_xyz": 5e-3, "_rotation": 1e-2, "_scaling": 1e-2, "_opacity": 2e-2, "verts_offset": 1e-3, "_features_dc": 1e-2,
+          "_features_rest": 5e-3, "shadow_map": 1e-2}
     opt = torch.optim.Adam([{"params": [p], "lr": lr[k], "name": k} for k, p in sc.params.items()], eps=1e-15)
     losses = []
     for step in range(a.steps + 1):

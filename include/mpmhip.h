@@ -348,6 +348,34 @@ int mpmhip_face_frames_backward(int32_t device, void *stream, const float *verts
                                 const float *g_face_orien_mat, const float *g_face_orien_quat, const float *g_face_scaling,
                                 const int32_t *vert_start, const int32_t *vert_corners, float *d_corners, float *d_verts);
 
+/* ---- the colours handed to the render call (train_appearance.py:120-123 and convert_SH, :31-47) ---------------------------------
+ *   out_colors [n*3] = shadow[binding[i]] * clamp_min(eval_sh(sh_degree, features[i], normalize(means3D[i] - campos)) + 0.5, 0)
+ *   shadow[f] = grid_sample(shadow_map [map_h*map_w], face_uv[f], bilinear, align_corners = False, zeros padding)
+ * features_dc [n*1*3] and features_rest [n*(n_sh_coeffs-1)*3] are GaussianModel's two tensors, read through two pointers (no cat);
+ * only the (sh_degree+1)^2 coefficients in use are read.  campos [3] and face_uv [n_faces*2] (in [-1, 1], v flipped,
+ * scene/mesh_gaussian_model.py:109-111) are device arrays.  shadow_map == NULL: shadow = 1, plain convert_SH; face_uv and binding
+ * may then be NULL.  features_dc == NULL: the colour before the shadow is (1, 1, 1), the shadow.repeat(1, 3) renders of
+ * train_appearance.py:215-226.  Both NULL is invalid.  A binding entry outside [0, n_faces) gives NaN and reads nothing.
+ * MPMHIP_ERR_INVALID, nothing launched: a negative count, sh_degree outside 0..3, n_sh_coeffs < (sh_degree+1)^2, a map size <= 0
+ * with a map, a required pointer NULL.  n == 0: MPMHIP_OK, no launch. */
+int mpmhip_shade_colors(int32_t device, void *stream, int32_t n, int32_t n_faces, const int32_t *binding, const float *means3D,
+                        const float *campos, int32_t sh_degree, int32_t n_sh_coeffs, const float *features_dc, const float *features_rest,
+                        const float *shadow_map, int32_t map_h, int32_t map_w, const float *face_uv, float *out_colors);
+/* mpmhip_shade_colors_backward: from g_colors [n*3] (NULL counts as zero) to d_features_dc, d_features_rest (zero above the active
+ * degree), d_means3D [n*3] and d_shadow_map [map_h*map_w]; each is written in full, NULL = not wanted.  The exact derivative with
+ * every discrete decision held fixed: the bilinear cell, a tap outside the map, and the SH clamp (zero slope where it binds); face_uv
+ * gets no gradient, as in train_appearance.py:120-123, where it is a constant.  fp32, no atomics, the same bits on every run:
+ * d_shadow_map walks two tables, needed only for it -- face_start [n_faces+1] / face_items [n] (the Gaussians of a face, ascending)
+ * and texel_start [map_h*map_w+1] / texel_items (4 * face + corner of every tap inside the map that lands on the texel, ascending;
+ * corner 0..3 = north-west, north-east, south-west, south-east) -- and scratch [n + n_faces] floats.  n == 0 still writes zeros
+ * to d_shadow_map. */
+int mpmhip_shade_colors_backward(int32_t device, void *stream, int32_t n, int32_t n_faces, const int32_t *binding, const float *means3D,
+                                 const float *campos, int32_t sh_degree, int32_t n_sh_coeffs, const float *features_dc,
+                                 const float *features_rest, const float *shadow_map, int32_t map_h, int32_t map_w, const float *face_uv,
+                                 const float *g_colors, float *d_features_dc, float *d_features_rest, float *d_means3D,
+                                 const int32_t *face_start, const int32_t *face_items, const int32_t *texel_start,
+                                 const int32_t *texel_items, float *d_shadow_map, float *scratch);
+
 /* MPMWARP.export_particle_cov_to_torch (warp_mpm/mpm_solver.py:543-561) = kernel compute_cov_from_F
  * (warp_mpm/mpm_utils.py:1108-1132): new_cov[6p..] = upper triangle (xx xy xz yy yz zz) of F_trial[p] * sym(particle_cov[6p..])
  * * F_trial[p]^T for p < n (= n_particles - n_vertices).  Stand-alone map on [dev] arrays in the reference's AoS layout. */

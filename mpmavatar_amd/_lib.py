@@ -105,6 +105,8 @@ SIGNATURES = {
     "mpmhip_render_inputs": (C.c_int, [C.c_int32, vp, C.c_int32, C.c_int32] + [vp] * 18),
     "mpmhip_render_inputs_backward": (C.c_int, [C.c_int32, vp, C.c_int32, C.c_int32] + [vp] * 22),
     "mpmhip_face_frames_backward": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, C.c_int32] + [vp] * 10),
+    "mpmhip_shade_colors": (C.c_int, [C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp]),
+    "mpmhip_shade_colors_backward": (C.c_int, [C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32] + [vp] * 11),
     "mpmhip_face_areas": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, vp]),
     "mpmhip_mesh_sample": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp]),
     "mpmhip_nn_dist2": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp]),

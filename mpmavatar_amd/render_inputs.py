@@ -49,6 +49,14 @@ class BoundGaussians:
     def get_features(self):  # gaussian_model.py:153-157
         return torch.cat((self._features_dc, self._features_rest), dim=1)
 
+    def shaded_colors(self, means3D, campos, active_sh_degree, shadow_map=None, sampler=None):
+        """-> colors [n, 3] for ``override_color`` (train_appearance.py:120-123): the model's SH features seen from ``campos`` at
+        ``means3D`` (the ``means3D`` of render_inputs, first n rows), times the shadow map sampled at each Gaussian's face
+        (``sampler``: shading.ShadowSampler) where one is given.  One launch, with a backward (mpmavatar_amd/shading.py)."""
+        from .shading import shaded_colors
+        return shaded_colors(self._features_dc, self._features_rest, active_sh_degree, means3D, campos, binding=self.binding,
+                             shadow_map=shadow_map, sampler=sampler, gtable=self._gtable)
+
     def render_inputs(self, frames: MeshFrames, override_color=None, extra=None):
         """-> dict of the rasteriser's keyword arguments (gaussian_renderer/__init__.py:94-102).  extra = (xyz [m,3], colors [m,3],
         opacity [m,1], scales [m,3], rotations [m,4]) as run_demo.py builds it (needs override_color, like the reference)."""
