@@ -9,6 +9,7 @@ import torch
 import binding_grad_cases as bc
 import image_loss_cases as ic
 import raster_scenes as rs
+import shade_cases as sc
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -86,7 +87,25 @@ def _nearest():
     return lambda: list(nearest_dist2(src, dst, return_index=True))
 
 
-CASES = {"mesh_frames+render_inputs": _binding, "image_loss": _image, "rasterizer": _raster, "geo_metrics": _nearest}
+def _shading():
+    """the smallest shading case (`k4`: 53 Gaussians on 11 faces, a 3 x 4 map, degree 1) through shaded_colors and its backward"""
+    from mpmavatar_amd.shading import ShadowSampler, shaded_colors
+    c = sc.case("k4")
+    base = {k: _t(c[k]) for k in sc.GRADS}
+    binding, campos, w = _t(c["binding"]), _t(c["campos"]), _t(c["w"])
+    H, W = c["shadow_map"].shape
+    sampler = ShadowSampler(_t(c["face_uv"]), H, W)
+
+    def run():
+        t = {k: _leaf(v) for k, v in base.items()}
+        colors = shaded_colors(t["features_dc"], t["features_rest"], 1, t["means3D"], campos, binding=binding, shadow_map=t["shadow_map"],
+                               sampler=sampler)
+        (w * colors).sum().backward()
+        return [colors.detach()] + [t[k].grad for k in sc.GRADS]
+    return run
+
+
+CASES = {"mesh_frames+render_inputs": _binding, "image_loss": _image, "rasterizer": _raster, "geo_metrics": _nearest, "shading": _shading}
 
 
 @pytest.mark.parametrize("module", sorted(CASES))
