@@ -9,14 +9,17 @@
                loss.backward()                              -> image loss, rasteriser, binding and face-frame backward kernels
                optimizer.step()                             (torch.optim.Adam, as the reference)
 
-    python examples/appearance_step_demo.py [--steps 30] [--size 64] [--colors]
+    python examples/appearance_step_demo.py [--steps 30] [--size 64] [--colors] [--reg]
 
 The mesh is a 320-face icosphere with two Gaussians per face.  The target image is rendered from perturbed parameters and perturbed
 vertices; Adam then moves ``_xyz``, ``_rotation``, ``_scaling``, ``_opacity`` and a per-vertex ``verts_offset`` towards it, and the
 loss it prints falls.  Without ``--colors`` the colours are fixed (``override_color``).  With it they are the reference's
 ``shadow * convert_SH(...)`` (train_appearance.py:120-123) in one more launch, ``gaussians.shaded_colors`` -> mpmhip_shade_colors:
 degree-1 SH features and an 8 x 8 shadow map (a leaf standing in for the output of the shadow network, which stays the caller's
-torch module) are leaves too, and the target is rendered from perturbed ones.
+torch module) are leaves too, and the target is rendered from perturbed ones.  With ``--reg`` the six regularisation terms of
+train_appearance.py:136-150 are added to the loss with the weights of train_appearance.py:87 and the thresholds of
+arguments/__init__.py:137-138, in two more calls, ``MeshRegularizer`` -> mpmhip_mesh_reg_forward and ``gaussian_regularizers`` ->
+mpmhip_gauss_reg_forward, and printed.
 """
 import argparse
 import os
@@ -30,23 +33,29 @@ from mpmavatar_amd import garment  # noqa: E402
 from mpmavatar_amd.image_loss import image_loss  # noqa: E402
 from mpmavatar_amd.mesh_frames import MeshFrames  # noqa: E402
 from mpmavatar_amd.rasterizer import GaussianRasterizationSettings, GaussianRasterizer, look_at_camera  # noqa: E402
+from mpmavatar_amd.regularizers import MeshRegularizer, gaussian_terms  # noqa: E402
 from mpmavatar_amd.render_inputs import BoundGaussians  # noqa: E402
 from mpmavatar_amd.shading import ShadowSampler  # noqa: E402
 
 PER_FACE = 2
 SH_DEGREE, MAP_SIZE = 1, 8
+REG_NAMES = ("normal", "iso", "eq_faces_weight", "opacity", "xyz", "scale")
+REG_WEIGHTS = (0.1, 20.0, 1000.0, 0.05, 1.0, 1.0)        # train_appearance.py:87
+THRESHOLD_XYZ, THRESHOLD_SCALE = 1.0, 0.6                # arguments/__init__.py:137-138
 
 
 class Scene:
     """Everything one training step needs; ``params`` are the five leaves the optimiser moves (eight with ``colors``)."""
 
-    def __init__(self, size=64, device="cuda:0", seed=0, eye=(0.0, 0.3, -2.0), colors=False):
+    def __init__(self, size=64, device="cuda:0", seed=0, eye=(0.0, 0.3, -2.0), colors=False, reg=False):
         dev = torch.device(device)
         g = torch.Generator(device="cpu").manual_seed(seed)
         rnd = lambda *s: torch.randn(*s, generator=g)
         verts, faces = garment.icosphere(2, 0.5, (0.0, 0.0, 0.0))
         self.verts_orig = torch.tensor(np.asarray(verts, np.float32), device=dev)
         self.frames = MeshFrames(torch.tensor(np.asarray(faces, np.int32), device=dev))
+        self.reg = MeshRegularizer(self.frames.faces, self.verts_orig) if reg else None
+        self.reg_weights, self.reg_terms = torch.tensor(REG_WEIGHTS, device=dev), None
         n_f = faces.shape[0]
         n = PER_FACE * n_f
         binding = torch.arange(n_f, dtype=torch.int32).repeat_interleave(PER_FACE).to(dev)
@@ -101,9 +110,16 @@ class Scene:
         return image, radii
 
     def loss(self):
-        """-> (loss, radii): train_appearance.py:132,134 without the LPIPS term"""
+        """-> (loss, radii): train_appearance.py:132,134 without the LPIPS term, plus the regularisers of :136-150 with ``reg``"""
         image, radii = self.render()
-        return image_loss(image, self.target, 0.2)[0], radii
+        loss = image_loss(image, self.target, 0.2)[0]
+        if self.reg is not None:
+            p = self.params
+            terms = torch.cat([self.reg.terms(self.frames.verts), gaussian_terms(p["_opacity"], p["_xyz"], p["_scaling"], radii, THRESHOLD_XYZ,
+                                                                                THRESHOLD_SCALE)])
+            self.reg_terms = terms.detach()
+            loss = loss + (self.reg_weights * terms).sum()
+        return loss, radii
 
 
 def main(argv=None):
@@ -111,8 +127,9 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--size", type=int, default=64)
     ap.add_argument("--colors", action="store_true", help="train SH features and a shadow map too (mpmhip_shade_colors)")
+    ap.add_argument("--reg", action="store_true", help="add the six weighted regularisation terms (mpmhip_mesh_reg_*, mpmhip_gauss_reg_*)")
     a = ap.parse_args(argv)
-    sc = Scene(a.size, colors=a.colors)
+    sc = Scene(a.size, colors=a.colors, reg=a.reg)
     lr = {"_xyz": 5e-3, "_rotation": 1e-2, "_scaling": 1e-2, "_opacity": 2e-2, "verts_offset": 1e-3, "_features_dc": 1e-2,
           "_features_rest": 5e-3, "shadow_map": 1e-2}
     opt = torch.optim.Adam([{"params": [p], "lr": lr[k], "name": k} for k, p in sc.params.items()], eps=1e-15)
@@ -123,6 +140,8 @@ def main(argv=None):
         losses.append(float(loss.detach()))
         if step % 5 == 0:
             print(f"step {step:3d}  loss {losses[-1]:.6f}  ({int((radii > 0).sum())} of {radii.numel()} Gaussians on screen)")
+            if a.reg:
+                print("          " + "  ".join(f"{k} {v:.3g}" for k, v in zip(REG_NAMES, sc.reg_terms.tolist())))
         if step == a.steps:
             break
         loss.backward()

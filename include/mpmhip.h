@@ -376,6 +376,58 @@ int mpmhip_shade_colors_backward(int32_t device, void *stream, int32_t n, int32_
                                  const int32_t *face_start, const int32_t *face_items, const int32_t *texel_start,
                                  const int32_t *texel_items, float *d_shadow_map, float *scratch);
 
+/* ---- the regularisation terms of the appearance loop (train_appearance.py:136-150) ------------------------------------------------
+ * What the reference computes between render(...) and loss.backward() besides the image loss, as two fused ops with exact backward
+ * passes.  Stand-alone maps on [dev] arrays; nothing allocates or synchronises; fp32 data, sums in fp64 in a fixed order, no
+ * floating-point atomics: the same input gives the same bits.  The weights of train_appearance.py:87 are the caller's.
+ *
+ * Mesh terms (scene/mesh_gaussian_model.py:203-246), K = MPMHIP_REG_K = 3 neighbours per face:
+ *   out_terms[0] normal = mean_f | mean_k(n_f . n_nb[f,k]) - 1 |,  n_f = d3 / |d3|, d3 = (v2 - v1) x (v3 - v1)      (normal_loss)
+ *   out_terms[1] iso    = mean_fk sqrt((sqrt(|c_nb[f,k] - c_f|^2 + 1e-20) - nd[f,k])^2 nw[f,k] + 1e-20)              (iso_loss)
+ *   out_terms[2] area   = mean_f | a_f - mean(a) |, a_f = |d3| / 2           (area_loss, the loop's "eq_faces_weight")
+ * face_neighbors [n_faces*3] is the array of find_adjacent_faces (utils/general_utils.py:286-316); a row may name its own face, as
+ * the reference pads boundary faces (:309-311): such a slot adds n_f . n_f to the mean and sqrt(1e-20 nw + 1e-20) to iso, and its
+ * gradient is exactly zero.  The array need not be symmetric.  neighbor_dist / neighbor_weight [n_faces*3] are the set-up of
+ * scene/mesh_gaussian_model.py:88-98; out_sq_dist [n_faces*3] or NULL receives |c_nb - c_f|^2 of every slot, from which that set-up
+ * is sqrt(.) and exp(-2000 .) (call once on verts_orig[0]; the two inputs play no part in it).  A zero-area face gives NaN in normal,
+ * as in the reference; an index outside its range gives NaN and reads nothing.  out_stats [2] = mean(a), mean(sign(a - mean(a))),
+ * which the backward pass reads.  scratch [MPMHIP_MESH_REG_SCRATCH(n_faces)] doubles.  n_faces == 0: MPMHIP_OK, nothing written.
+ * MPMHIP_ERR_INVALID, nothing launched: a negative count, 36 * n_faces > 2^31 - 1, a required pointer NULL. */
+#define MPMHIP_REG_K 3
+#define MPMHIP_REG_TPB 256
+#define MPMHIP_MESH_REG_SCRATCH(n_faces) (3 * (((int64_t)(n_faces) + MPMHIP_REG_TPB - 1) / MPMHIP_REG_TPB) + ((int64_t)(n_faces) + 1) / 2)
+int mpmhip_mesh_reg_forward(int32_t device, void *stream, const float *verts, int32_t n_verts, const int32_t *faces, int32_t n_faces,
+                            const int32_t *face_neighbors, const float *neighbor_dist, const float *neighbor_weight, double *scratch,
+                            float *out_terms, float *out_stats, float *out_sq_dist);
+/* mpmhip_mesh_reg_backward: from g_terms [3] on the device (the upstream gradients of normal, iso, area; no value passes through
+ * the host) to d_verts [n_verts*3], written in full; NULL = not wanted, nothing launched.  The exact derivative with every discrete
+ * decision held fixed (sign(0) = 0 inside the absolute values); d area / d a_f = (sign(a_f - mean) - stats[1]) / n_faces.  Row f of
+ * the loss touches a stencil of 1 + K faces x 3 corners, S[f, s, c] = faces[nbx[f, s], c] with nbx[f, 0] = f, nbx[f, 1 + k] =
+ * face_neighbors[f, k]: d_stencil [n_faces*36] is scratch for the gradient of each of those corners, and vert_start [n_verts+1] /
+ * vert_items [12*n_faces] is the vertex -> stencil item table (item = 12 f + 3 s + c, ascending within a vertex), which a vertex
+ * walks serially.  A vertex in no face gets exactly 0.  stats [2]: the forward's, for the same verts. */
+int mpmhip_mesh_reg_backward(int32_t device, void *stream, const float *verts, int32_t n_verts, const int32_t *faces, int32_t n_faces,
+                             const int32_t *face_neighbors, const float *neighbor_dist, const float *neighbor_weight, const float *stats,
+                             const float *g_terms, const int32_t *vert_start, const int32_t *vert_items, float *d_stencil, float *d_verts);
+/* Gaussian terms (train_appearance.py:138,147,148; opacity_loss is scene/mesh_gaussian_model.py:222-223 over get_opacity,
+ * scene/gaussian_model.py:158), visible = radii[i] > 0 (the rasteriser's int32 radii) or visible[i] != 0 (a byte mask): exactly one
+ * of the two pointers is given.
+ *   out_terms[0] opacity = mean(1 - sigmoid(opacity [n]))
+ *   out_terms[1] xyz     = mean over visible of relu(|xyz[i]| - threshold_xyz)                      xyz, scaling [n*3]
+ *   out_terms[2] scale   = mean over visible of | relu(exp(scaling[i]) - threshold_scale) |_2
+ * out_n_visible [1]: the count, kept on the device for the backward pass.  No visible row: NaN for xyz and scale (0 / 0, the
+ * reference's mean of an empty tensor).  scratch [MPMHIP_GAUSS_REG_SCRATCH(n)] doubles.  n == 0: MPMHIP_OK, nothing written. */
+#define MPMHIP_GAUSS_REG_SCRATCH(n) (4 * (((int64_t)(n) + MPMHIP_REG_TPB - 1) / MPMHIP_REG_TPB))
+int mpmhip_gauss_reg_forward(int32_t device, void *stream, int32_t n, const float *opacity, const float *xyz, const float *scaling,
+                             const int32_t *radii, const uint8_t *visible, float threshold_xyz, float threshold_scale, double *scratch,
+                             float *out_terms, int32_t *out_n_visible);
+/* mpmhip_gauss_reg_backward: from g_terms [3] on the device to d_opacity [n], d_xyz [n*3], d_scaling [n*3], each written in full,
+ * NULL = not wanted.  A relu that binds has zero slope, the norm of an all-zero row has zero slope, a row outside the visible set
+ * gets exact zeros for xyz and scale (so with no visible row every such gradient is zero). */
+int mpmhip_gauss_reg_backward(int32_t device, void *stream, int32_t n, const float *opacity, const float *xyz, const float *scaling,
+                              const int32_t *radii, const uint8_t *visible, float threshold_xyz, float threshold_scale,
+                              const int32_t *n_visible, const float *g_terms, float *d_opacity, float *d_xyz, float *d_scaling);
+
 /* MPMWARP.export_particle_cov_to_torch (warp_mpm/mpm_solver.py:543-561) = kernel compute_cov_from_F
  * (warp_mpm/mpm_utils.py:1108-1132): new_cov[6p..] = upper triangle (xx xy xz yy yz zz) of F_trial[p] * sym(particle_cov[6p..])
  * * F_trial[p]^T for p < n (= n_particles - n_vertices).  Stand-alone map on [dev] arrays in the reference's AoS layout. */

@@ -107,7 +107,11 @@ SIGNATURES = {
     "mpmhip_face_frames_backward": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, C.c_int32] + [vp] * 10),
     "mpmhip_shade_colors": (C.c_int, [C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp]),
     "mpmhip_shade_colors_backward": (C.c_int, [C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32] + [vp] * 11),
-    "mpmhip_face_areas": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, vp]),
+    "mpmhip_mesh_reg_forward": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32] + [vp] * 7),
+    "mpmhip_mesh_reg_backward": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32] + [vp] * 9),
+    "mpmhip_gauss_reg_forward": (C.c_int, [C.c_int32, vp, C.c_int32] + [vp] * 5 + [C.c_float, C.c_float] + [vp] * 3),
+    "mpmhip_gauss_reg_backward": (C.c_int, [C.c_int32, vp, C.c_int32] + [vp] * 5 + [C.c_float, C.c_float] + [vp] * 5),
+    "mpmhip_face_areas":(C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, vp]),
     "mpmhip_mesh_sample": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp]),
     "mpmhip_nn_dist2": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp]),
     "mpmhip_geo_reduce": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_double, vp, vp]),
