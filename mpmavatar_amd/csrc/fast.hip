@@ -276,6 +276,46 @@ void materialize_grid(mpmhip_ctx *c, bool count) {
 }
 
 
+// Every environment switch the context reads at creation, in one place (DESIGN.md section 10 lists them, and the ones resort.hip and
+// dist.hip read later, at run time).  Defaults that depend on the scene are set here too, in front of their switch.
+static void read_switches(const mpmhip_config &cfg, FastState *f) {
+  int cell_bits = f->blk_bits_plain + 8 + 2 + 2 <= 32 ? 8 : 6;  // 8: predictive sort (see make_key)
+  if (const char *e = getenv("MPMHIP_PREDICTIVE_SORT")) if (atoi(e) == 0) cell_bits = 6;
+  f->key_bits = f->blk_bits_plain + cell_bits + 2 + 2;
+  f->blk_bits = f->blk_bits_plain | (cell_bits << 8);
+  if (const char *e = getenv("MPMHIP_SORT")) f->sort_rocprim = std::string(e) == "rocprim";
+  f->p2g_fixed = cfg.p2g_tile != MPMHIP_P2G_TILE_F64;
+  f->p2g_fixed_forced = cfg.p2g_tile == MPMHIP_P2G_TILE_FIXED;
+  if (const char *e = getenv("MPMHIP_P2G_TILE")) { f->p2g_fixed = std::string(e) != "f64"; f->p2g_fixed_forced = std::string(e) == "fx"; }
+  f->p2g_fixed_now = f->p2g_fixed;
+  if (const char *e = getenv("MPMHIP_G2P2G")) f->g2p2g = atoi(e) != 0;
+  if (const char *e = getenv("MPMHIP_COL_KEEP")) f->col_keep = atoi(e) != 0;
+  if (const char *e = getenv("MPMHIP_SPLIT_SPLAT")) f->split_splat = atoi(e) != 0;
+  if (const char *e = getenv("MPMHIP_SPLIT_SPLAT_MAX")) f->split_splat_max_chunks = atoi(e);
+  if (const char *e = getenv("MPMHIP_G2P2G_MAX")) f->g2p2g_max_chunks = atoi(e);
+  if (const char *e = getenv("MPMHIP_DBG")) f->g.dbg = MPMHIP_DEBUG ? (int)strtoul(e, nullptr, 0) : ((int)strtoul(e, nullptr, 0) & 64);
+  if (const char *e = getenv("MPMHIP_FUSE_GRID")) f->fuse_grid = atoi(e) != 0;
+  f->g2p_two_pass = cfg.n_particles - cfg.n_elements - cfg.n_vertices == 0;
+  if (const char *e = getenv("MPMHIP_G2P_TWO_PASS")) f->g2p_two_pass = atoi(e) != 0;
+  if (const char *e = getenv("MPMHIP_FUSE_TRAD")) f->fuse_trad = atoi(e) != 0;
+  if (const char *e = getenv("MPMHIP_DIST_FUSED_HALO")) f->fused_want = atoi(e) != 0;
+  // p2g's first round staggered by wave slot -- 2 x 1024 cycles per step, 5 groups, the first 1,280 workgroups -- where the launch is
+  // more than two rounds of workgroups (decided per launch in step_phase_a): the headline scene +1.1 % at t = 0 and draped (round 4,
+  // three alternating runs: 16.06-16.08 k -> 16.21-16.29 k; round 3 had measured the same and left it off because a launch of less
+  // than one round loses up to 20 %).  MPMHIP_P2G_STAGGER="units[,groups[,first]]" forces a setting for every launch, "0" none.
+  f->g.stagger = 0; f->g.stagger_groups = 5; f->g.stagger_first = 1280;
+  f->stagger_auto = 2;
+  if (const char *e = getenv("MPMHIP_P2G_STAGGER")) {
+    int u = 0, gr = 2, first = 1280;
+    sscanf(e, "%d,%d,%d", &u, &gr, &first);
+    f->g.stagger = std::max(0, u); f->g.stagger_groups = std::max(1, gr); f->g.stagger_first = std::max(0, first);
+    f->stagger_auto = -1;  // forced
+  }
+  if (const char *e = getenv("MPMHIP_HOST_LEAD")) f->host_lead = std::min(std::max(1, atoi(e)), 12);  // (ring of 16 entries)
+  f->g.lookahead = DRIFT_LOOKAHEAD;
+  if (const char *e = getenv("MPMHIP_DRIFT_LOOKAHEAD")) f->g.lookahead = (float)atof(e);
+}
+
 int fast_init(mpmhip_ctx *c) {
   const mpmhip_config &cfg = c->cfg;
   if (cfg.n_grid > 512) return fail(c, MPMHIP_ERR_INVALID, "fast mode supports n_grid <= 512");
@@ -288,21 +328,8 @@ int fast_init(mpmhip_ctx *c) {
   f->nblocks = (size_t)d.NB * d.NB * d.NB;
   f->blk_bits_plain = 1;
   while ((1ull << f->blk_bits_plain) < f->nblocks) ++f->blk_bits_plain;
-  int cell_bits = f->blk_bits_plain + 8 + 2 + 2 <= 32 ? 8 : 6;  // 8: predictive sort (see make_key)
-  if (const char *e = getenv("MPMHIP_PREDICTIVE_SORT")) if (atoi(e) == 0) cell_bits = 6;
-  if (const char *e = getenv("MPMHIP_SORT")) f->sort_rocprim = std::string(e) == "rocprim";
-  f->p2g_fixed = cfg.p2g_tile != MPMHIP_P2G_TILE_F64;
-  f->p2g_fixed_forced = cfg.p2g_tile == MPMHIP_P2G_TILE_FIXED;
-  if (const char *e = getenv("MPMHIP_P2G_TILE")) { f->p2g_fixed = std::string(e) != "f64"; f->p2g_fixed_forced = std::string(e) == "fx"; }
-  f->p2g_fixed_now = f->p2g_fixed;
-  if (const char *e = getenv("MPMHIP_G2P2G")) f->g2p2g = atoi(e) != 0;
-  if (const char *e = getenv("MPMHIP_COL_KEEP")) f->col_keep = atoi(e) != 0;
-  if (const char *e = getenv("MPMHIP_SPLIT_SPLAT")) f->split_splat = atoi(e) != 0;
-  if (const char *e = getenv("MPMHIP_SPLIT_SPLAT_MAX")) f->split_splat_max_chunks = atoi(e);
-  if (const char *e = getenv("MPMHIP_G2P2G_MAX")) f->g2p2g_max_chunks = atoi(e);
-  f->key_bits = f->blk_bits_plain + cell_bits + 2 + 2;
+  read_switches(cfg, f);
   if (f->key_bits > 32) return fail(c, MPMHIP_ERR_INVALID, "grid too large for 32-bit sort keys");
-  f->blk_bits = f->blk_bits_plain | (cell_bits << 8);
   // upper bound between re-sorts; the drift flag normally triggers one earlier (or never, for slow scenes)
   f->rebin_interval = cfg.rebin_interval > 0 ? cfg.rebin_interval : (cfg.rebin_interval < 0 ? -cfg.rebin_interval : 256);
   f->adaptive_rebin = cfg.rebin_interval >= 0;
@@ -335,37 +362,13 @@ int fast_init(mpmhip_ctx *c) {
   if ((rc = dalloc(c, &f->pb_index, f->nblocks))) return rc;
   if ((rc = dalloc(c, &f->ab_index, f->nblocks))) return rc;
   f->g.ab_flag = f->ab_flag;
-  if (const char *e = getenv("MPMHIP_DBG")) f->g.dbg = MPMHIP_DEBUG ? (int)strtoul(e, nullptr, 0) : ((int)strtoul(e, nullptr, 0) & 64);
-  if (const char *e = getenv("MPMHIP_FUSE_GRID")) f->fuse_grid = atoi(e) != 0;
-  f->g2p_two_pass = cfg.n_particles - cfg.n_elements - cfg.n_vertices == 0;
-  if (const char *e = getenv("MPMHIP_G2P_TWO_PASS")) f->g2p_two_pass = atoi(e) != 0;
-  if (const char *e = getenv("MPMHIP_FUSE_TRAD")) f->fuse_trad = atoi(e) != 0;
-  if (const char *e = getenv("MPMHIP_DIST_FUSED_HALO")) f->fused_want = atoi(e) != 0;
-  if (const char *e = getenv("MPMHIP_SPLAT_FIRST_MAX")) f->splat_first_max = atoi(e);
-  // p2g's first round staggered by wave slot -- 2 x 1024 cycles per step, 5 groups, the first 1,280 workgroups -- where the launch is
-  // more than two rounds of workgroups (decided per launch in step_phase_a): the headline scene +1.1 % at t = 0 and draped (round 4,
-  // three alternating runs: 16.06-16.08 k -> 16.21-16.29 k; round 3 had measured the same and left it off because a launch of less
-  // than one round loses up to 20 %).  MPMHIP_P2G_STAGGER="units[,groups[,first]]" forces a setting for every launch, "0" none.
-  f->g.stagger = 0; f->g.stagger_groups = 5; f->g.stagger_first = 1280;
-  f->stagger_auto = 2;
-  if (const char *e = getenv("MPMHIP_P2G_STAGGER")) {
-    int u = 0, gr = 2, first = 1280;
-    sscanf(e, "%d,%d,%d", &u, &gr, &first);
-    f->g.stagger = std::max(0, u); f->g.stagger_groups = std::max(1, gr); f->g.stagger_first = std::max(0, first);
-    f->stagger_auto = -1;  // forced
-  }
   MPM_HIP_CHECK(c, hipHostMalloc((void **)&f->h_pin, PIN_N * sizeof(int), hipHostMallocDefault));
-  {
-    int *hs = nullptr, *ds = nullptr;
-    MPM_HIP_CHECK(c, hipHostMalloc((void **)&hs, SIG_WORDS * sizeof(int), hipHostMallocMapped));
-    memset(hs, 0, SIG_WORDS * sizeof(int));
-    MPM_HIP_CHECK(c, hipHostGetDevicePointer((void **)&ds, hs, 0));
-    f->h_sig = hs;
-    f->g.host_sig = ds;
-    if (const char *e = getenv("MPMHIP_HOST_LEAD")) f->host_lead = std::min(std::max(1, atoi(e)), 12);  // (ring of 16 entries)
-    f->g.lookahead = DRIFT_LOOKAHEAD;
-    if (const char *e = getenv("MPMHIP_DRIFT_LOOKAHEAD")) f->g.lookahead = (float)atof(e);
-  }
+  int *hs = nullptr, *ds = nullptr;
+  MPM_HIP_CHECK(c, hipHostMalloc((void **)&hs, SIG_WORDS * sizeof(int), hipHostMallocMapped));
+  memset(hs, 0, SIG_WORDS * sizeof(int));
+  MPM_HIP_CHECK(c, hipHostGetDevicePointer((void **)&ds, hs, 0));
+  f->h_sig = hs;
+  f->g.host_sig = ds;
   return MPMHIP_OK;
 }
 
@@ -443,7 +446,7 @@ int flush_g2p(mpmhip_ctx *c) {
 }
 
 // Look at the drift flags the device has posted (ring in pinned host memory) and turn a raised flag into "re-sort before the next
-// substep" (steps_since_rebin = 1 << 30).  Called once per substep, at the head of step_phase_a.
+// substep" (steps_since_rebin = 1 << 30).  Called once per substep, by poll_and_resort.
 static int poll_drift_flags(mpmhip_ctx *c) {
   FastState *f = c->fast;
   // the kernels report progress and their flags into pinned host memory (k_p2g): no stream operation here.  Before
@@ -471,29 +474,36 @@ static int poll_drift_flags(mpmhip_ctx *c) {
   return MPMHIP_OK;
 }
 
-int step_phase_a(mpmhip_ctx *c, const StepArgs &a) {
+// ---- step_phase_a in its parts, in the order they run ------------------------------------------------------------------------
+// the caller's state in; what earlier substeps deferred and this one cannot take over is flushed
+static int import_and_flush(mpmhip_ctx *c, float dt) {
   FastState *f = c->fast;
-  const Dims &d = f->d;
-  hipStream_t s = c->stream;
   int rc;
   if (c->caller_dirty) {
     if (f->dist) return fail(c, MPMHIP_ERR_STATE, "dist mode: call mpmhip_dist_rebin after (re)binding the state");
     if ((rc = do_import(c))) return rc;
   }
-  const float dt = a.dt;
-  if (!f->acc.body_at_rest()) f->acc.invalidate_kept_fields(s);   // (fields kept by an mpmhip_steps call whose body was at rest: this body may move)
-  // pre-p2g particle operations, mpm_solver.py:260-279 (impulses first, then velocity modifiers)
+  if (!f->acc.body_at_rest()) f->acc.invalidate_kept_fields(c->stream);   // (fields kept by an mpmhip_steps call whose body was at rest: this body may move)
   if (f->g2p_pending && (!g2p2g_ok(c) || !c->pre.empty() || dt != f->pend_dt)) flush_g2p(c);
-  if (!c->pre.empty() && d.n_p) {
-    flush_elements(c);
-    float t = (float)c->time;
-    for (int pass = 0; pass < 2; ++pass)
-      for (auto &op : c->pre) {
-        bool imp = op.type == PRE_IMPULSE || op.type == PRE_IMPULSE_MASK;
-        if (imp != (pass == 0) || !(t >= op.start_time && t < op.end_time)) continue;
-        hipLaunchKernelGGL(k_pre_sorted, nblk(d.n_p), TPB, 0, s, op, f->buf[f->cur], f->perm[f->cur], d, dt);
-      }
-  }
+  return MPMHIP_OK;
+}
+// pre-p2g particle operations, mpm_solver.py:260-279 (impulses first, then velocity modifiers)
+static void run_pre_ops(mpmhip_ctx *c, float dt) {
+  FastState *f = c->fast;
+  const Dims &d = f->d;
+  if (c->pre.empty() || !d.n_p) return;
+  flush_elements(c);
+  float t = (float)c->time;
+  for (int pass = 0; pass < 2; ++pass)
+    for (auto &op : c->pre) {
+      bool imp = op.type == PRE_IMPULSE || op.type == PRE_IMPULSE_MASK;
+      if (imp != (pass == 0) || !(t >= op.start_time && t < op.end_time)) continue;
+      hipLaunchKernelGGL(k_pre_sorted, nblk(d.n_p), TPB, 0, c->stream, op, f->buf[f->cur], f->perm[f->cur], d, dt);
+    }
+}
+static int poll_and_resort(mpmhip_ctx *c, float dt) {
+  FastState *f = c->fast;
+  int rc;
   if (!f->dist) {
     // Drift flag raised by g2p / element finalise / collider splat.  Reading it also bounds how far the host may run
     // ahead of the GPU (host_lead substeps) -- otherwise a fused mpmhip_steps(n) would have enqueued all n substeps
@@ -510,55 +520,63 @@ int step_phase_a(mpmhip_ctx *c, const StepArgs &a) {
   }
   f->last_dt = dt;
   f->true_since_rebin += 1;
-  // The body-face and joint splats ride along in the p2g launch as extra workgroups (SplatArgs).  With profiling on
-  // (one sync per phase, like the reference's ScopedTimer) they get a launch of their own under the reference's
-  // phase names: the same kernel with no particle chunks.
-  bool has_col = !c->colliders.empty() && c->num_mesh_f && f->n_fbins;
-  bool mov_on = a.joint_v_v && a.joint_f_v && !c->movers.empty();
-  // traditional particles: their stress update runs at the front of p2g (k_p2g<.., true, ..>) unless profiling wants
-  // the reference's phases apart
-  const bool trad_fused = d.n_t > 0 && f->fuse_trad && !c->profiling;
-  const TradParams tp{c->sc.material, c->sc.alpha, c->sc.hardening, c->sc.xi, c->sc.plastic_viscosity, c->sc.softening};
-  bool jt_tile = false;
-  SplatArgs sa{};
-  SplatArgs none{};
-  none.z_first = 1 << 30;
+  return MPMHIP_OK;
+}
+
+// What rides in this substep's launches, decided in one place.  The body-face and joint splats ride along in the p2g launch as extra
+// workgroups (SplatArgs), with the clearing of the accumulators the last substep left loaded and, in sharded runs, the halo pack;
+// `lay` says where each kind begins.  With profiling on (one sync per phase, like the reference's ScopedTimer) every kind gets a
+// launch of its own under the reference's phase names: the same kernel, the same layout function, no particle chunks.
+struct RiderPlan {
+  SplatArgs sa;
+  LaunchLayout lay;
+  GridRead rd;        // (fused launch) the buffer the deferred g2p reads
+  bool trad_fused;    // traditional particles: their stress update runs at the front of p2g (k_p2g<.., true, ..>)
+  bool jt_tile;       // many held traditional particles: splatted through the p2g tiles (needs the fused-stress kernel variant)
+  bool do_g2p2g;      // this launch also runs the deferred g2p of the last substep (k_g2p2g)
+  bool split_splat;   // the body-face splat's first pass rides in front of the stress launch
+};
+static RiderPlan plan_riders(mpmhip_ctx *c, const StepArgs &a) {
+  FastState *f = c->fast;
+  const Dims &d = f->d;
+  RiderPlan p{};
+  SplatArgs &sa = p.sa;
+  const bool has_col = !c->colliders.empty() && c->num_mesh_f && f->n_fbins;
+  const bool mov_on = a.joint_v_v && a.joint_f_v && !c->movers.empty();
+  // (profiling wants the reference's phases apart)
+  p.trad_fused = d.n_t > 0 && f->fuse_trad && !c->profiling;
+  int n_fbins = 0, n_joint = 0;
   if (has_col) {
     sa.pts = c->cur_pts; sa.vel = c->cur_vel; sa.adv = c->cur_f; sa.fidx = f->fidx; sa.fbins = f->fbins;
-    sa.n_fbins = f->n_fbins;
+    n_fbins = f->n_fbins;
   }
   if (mov_on) {
     sa.js = JointSplatArgs{a.joint_t_v, a.joint_v_v, a.joint_f_v, (a.joint_t_v ? a.n_joint_t : 0), c->cfg.num_joint_v,
                            c->cfg.num_joint_f, d.n_nv - a.n_joint_t, d.n_nv, f->inv, f->perm[f->cur], 0};
-    // many held traditional particles: splatted through the p2g tiles (needs the fused-stress kernel variant)
-    jt_tile = trad_fused && sa.js.n_t >= 2048;
-    sa.js.t_in_tile = jt_tile ? 1 : 0;
-    int nj = (jt_tile ? 0 : sa.js.n_t) + sa.js.n_v + sa.js.n_f;
-    sa.n_mov_wg = (int)(((size_t)nj * 32 + PT - 1) / PT);
-    if (nj == 0) sa.n_mov_wg = 0;
+    p.jt_tile = p.trad_fused && sa.js.n_t >= 2048;
+    sa.js.t_in_tile = p.jt_tile ? 1 : 0;
+    const int nj = (p.jt_tile ? 0 : sa.js.n_t) + sa.js.n_v + sa.js.n_f;
+    n_joint = (int)(((size_t)nj * 32 + PT - 1) / PT);
   }
   // accumulators left loaded by the previous (fused) substep: this substep scatters into the other buffer and clears
   // the loaded one with extra workgroups of the p2g launch
-  const bool do_g2p2g = f->g2p_pending && !jt_tile;  // (pending survives a re-sort decision above only when none happened)
-  if (f->g2p_pending && !do_g2p2g) flush_g2p(c);
-  GridRead rd{f->g.mv, f->g.col, f->g.mov, f->g.col_flag};  // (fused launch) the buffer the deferred g2p reads: the current one
+  p.do_g2p2g = f->g2p_pending && !p.jt_tile;  // (pending survives a re-sort decision above only when none happened)
+  if (f->g2p_pending && !p.do_g2p2g) flush_g2p(c);
+  p.rd = GridRead{f->g.mv, f->g.col, f->g.mov, f->g.col_flag};  // the current one
   // (profiling runs keep one launch per reference phase: they clear with a launch of their own)
-  sa.z = do_g2p2g ? f->acc.begin_fused_substep() : f->acc.begin_substep(s, c->profiling);
+  sa.z = p.do_g2p2g ? f->acc.begin_fused_substep() : f->acc.begin_substep(c->stream, c->profiling);
   // a body at rest whose collider field the buffer already holds: no splat workgroups in this substep
   if (has_col && f->acc.collider_substep(f->acc.body_at_rest() && !c->profiling)) {
-    sa.n_fbins = 0;
+    n_fbins = 0;
     f->n_col_kept += 1;
   }
   // cloth scenes of the production loop: the splat's first pass rides in front of the stress launch (col_splat_wg)
   // ... where the p2g launch is at most one round of workgroups, i.e. as long as a workgroup's life is the launch's length
   // (garment-120k-aniso: stress 9.7 -> 12.0 us, p2g 20.0 -> 16.4 us, 24.7 k -> 25.6 k substeps/s; with several rounds of chunk
   // workgroups the splat hides among them and the split only lengthens the stress launch: sheet-500k -1 %, profiles/r04_experiments.md)
-  const bool split_splat = f->split_splat && has_col && sa.n_fbins > 0 && d.n_e > 0 && f->elem_pending && !c->profiling && !f->dist &&
-                           f->n_chunks <= f->split_splat_max_chunks && !(MPMHIP_DEBUG && f->g.dbg);
-  sa.splat_passes = split_splat ? 2 : 3;
-  sa.n_extra = (sa.n_fbins + sa.n_mov_wg + 7) & ~7;
-  sa.z_first = sa.n_extra + (int)xcd_grid(f->n_chunks);
-  sa.e0 = (sa.n_extra > f->splat_first_max && !c->profiling) ? (int)xcd_grid(f->n_chunks) : 0;
+  p.split_splat = f->split_splat && has_col && n_fbins > 0 && d.n_e > 0 && f->elem_pending && !c->profiling && !f->dist &&
+                  f->n_chunks <= f->split_splat_max_chunks && !(MPMHIP_DEBUG && f->g.dbg);
+  sa.splat_passes = p.split_splat ? 2 : 3;
   const bool fused_halo_now = f->dist && f->fused_halo && !c->profiling && !c->prof_fused;
   if (fused_halo_now) {  // (multi-GPU) the halo pack rides in this launch, behind the clearing workgroups: see PackArgs
     HaloTab &tb = sa.pack.tb;
@@ -575,56 +593,75 @@ int step_phase_a(mpmhip_ctx *c, const StepArgs &a) {
     }
     tb.seq = (int)f->halo_seq;
     sa.pack.n_wg = tb.wg_off[tb.n];
-    sa.pack.first = sa.z_first + sa.z.n_wg;
+  }
+  p.lay = launch_layout(n_fbins, n_joint, f->n_chunks, sa.z.n_wg, sa.pack.n_wg);
+  set_layout(sa, p.lay);
+  if (fused_halo_now) {
     sa.pack.count = 1;
     sa.pack.done = f->pack_done;
-    f->pack_target += (unsigned)sa.z_first;  // every workgroup in front of the clearing ones counts itself done
+    f->pack_target += (unsigned)p.lay.n_scatter();
     sa.pack.target = f->pack_target;
   }
-  f->g.step_id = (int)++f->sig_seq;
-  if (f->stagger_auto >= 0) f->g.stagger = (f->n_chunks >= 2 * 1280 && !c->profiling) ? f->stagger_auto : 0;
-  const bool stress_here = d.n_e > 0;
-  if (stress_here || (d.n_t && !trad_fused)) {  // (no empty event bracket when the stress update rides in p2g)
-    ScopedPhase ph(c, "compute_stress_from_F_trial");
-    if (stress_here) {
-      launch_stress_elem(c, split_splat ? 2 : (f->elem_pending ? 1 : 0), sa);
-      f->elem_pending = false;
-    }
-    if (d.n_t && !trad_fused) launch_stress_trad(c, dt);
+  return p;
+}
+static void issue_stress(mpmhip_ctx *c, const RiderPlan &p, float dt) {
+  FastState *f = c->fast;
+  const Dims &d = f->d;
+  const bool trad_here = d.n_t && !p.trad_fused;
+  if (!(d.n_e > 0 || trad_here)) return;  // (no empty event bracket when the stress update rides in p2g)
+  ScopedPhase ph(c, "compute_stress_from_F_trial");
+  if (d.n_e > 0) {
+    launch_stress_elem(c, p.split_splat ? 2 : (f->elem_pending ? 1 : 0), p.sa);
+    f->elem_pending = false;
   }
-  if (c->profiling && sa.n_extra) {
+  if (trad_here) launch_stress_trad(c, dt);
+}
+// profiled (one launch per reference phase) / fused with the deferred g2p / plain
+static void issue_scatter(mpmhip_ctx *c, const RiderPlan &p, float dt) {
+  FastState *f = c->fast;
+  const TradParams tp{c->sc.material, c->sc.alpha, c->sc.hardening, c->sc.xi, c->sc.plastic_viscosity, c->sc.softening};
+  if (c->profiling && p.lay.n_riders) {
+    auto alone = [&](int n_fbins, int n_joint, int n_chunks) {  // one kind of workgroup in a launch of its own
+      const LaunchLayout one = launch_layout(n_fbins, n_joint, n_chunks, 0, 0);
+      SplatArgs sa = p.sa;
+      set_layout(sa, one);
+      launch_p2g(c, false, false, one.grid(), n_chunks, dt, sa, tp);
+    };
     {
       ScopedPhase ph(c, "p2g");
-      if (f->n_chunks)
-        launch_p2g(c, false, false, xcd_grid(f->n_chunks), f->n_chunks, dt, none, tp);
+      if (f->n_chunks) alone(0, 0, f->n_chunks);
     }
-    if (sa.n_fbins) {
+    if (p.lay.n_fbins) {
       ScopedPhase ph(c, "apply_Mesh_Collision_on_grid");
-      SplatArgs only = sa;
-      only.n_mov_wg = 0;
-      only.n_extra = (only.n_fbins + 7) & ~7;
-      only.z_first = 1 << 30;
-      launch_p2g(c, false, false, (unsigned)only.n_extra, 0, dt, only, tp);
+      alone(p.lay.n_fbins, 0, 0);
     }
-    if (sa.n_mov_wg) {
+    if (p.lay.n_joint) {
       ScopedPhase ph(c, "apply_Particle_Moving_on_grid");
-      SplatArgs only = sa;
-      only.n_fbins = 0;
-      only.n_extra = (only.n_mov_wg + 7) & ~7;
-      only.z_first = 1 << 30;
-      launch_p2g(c, false, false, (unsigned)only.n_extra, 0, dt, only, tp);
+      alone(0, p.lay.n_joint, 0);
     }
-  } else if (do_g2p2g) {
+  } else if (p.do_g2p2g) {
     ScopedPhase ph(c, "g2p2g");
-    const unsigned grid = xcd_grid(f->n_chunks) + (unsigned)(sa.n_extra + sa.z.n_wg);
-    launch_g2p2g(c, grid, dt, rd, sa, tp, f->pend_gp, f->pend_bcl);
+    launch_g2p2g(c, p.lay.grid(), dt, p.rd, p.sa, tp, f->pend_gp, f->pend_bcl);
     f->g2p_pending = false;
     f->n_g2p2g += 1;
   } else {
     ScopedPhase ph(c, "p2g");
-    if (f->n_chunks || sa.n_extra || sa.z.n_wg || sa.pack.n_wg)
-      launch_p2g(c, trad_fused, jt_tile, xcd_grid(f->n_chunks) + (unsigned)(sa.n_extra + sa.z.n_wg + sa.pack.n_wg), f->n_chunks, dt, sa, tp);
+    if (p.lay.grid()) launch_p2g(c, p.trad_fused, p.jt_tile, p.lay.grid(), f->n_chunks, dt, p.sa, tp);
   }
+}
+
+int step_phase_a(mpmhip_ctx *c, const StepArgs &a) {
+  FastState *f = c->fast;
+  const float dt = a.dt;
+  int rc;
+  if ((rc = import_and_flush(c, dt))) return rc;
+  run_pre_ops(c, dt);
+  if ((rc = poll_and_resort(c, dt))) return rc;
+  const RiderPlan plan = plan_riders(c, a);
+  f->g.step_id = (int)++f->sig_seq;
+  if (f->stagger_auto >= 0) f->g.stagger = (f->n_chunks >= 2 * 1280 && !c->profiling) ? f->stagger_auto : 0;
+  issue_stress(c, plan, dt);
+  issue_scatter(c, plan, dt);
   return MPMHIP_OK;
 }
 

@@ -20,6 +20,7 @@
 
 #include "bc.hpp"
 #include "ctx.hpp"
+#include "launch_layout.hpp"
 #include "mpm_math.hpp"
 
 namespace mpm {
@@ -112,20 +113,6 @@ __device__ __forceinline__ int loc_of(int x, int y, int z) { return ((x & 3) << 
 __device__ __forceinline__ bool in_grid(int x, int y, int z, int G) {
   return (unsigned)x < (unsigned)G && (unsigned)y < (unsigned)G && (unsigned)z < (unsigned)G;
 }
-// XCD-aware remap: consecutive workgroup ids land on different XCDs (observed: id % 8).  Work items are sorted by
-// grid block, so runs of XCD_RUN consecutive items (neighbouring tiles) are given to the same XCD to share its L2,
-// while successive runs rotate over the 8 XCDs so that a spatially concentrated load (e.g. the blocks around the
-// body collider) is spread over the whole chip instead of landing on one or two XCDs.
-#ifndef MPM_XCD_RUN
-#define MPM_XCD_RUN 16  // (experiment switch; 8 and 32 measured in round 5)
-#endif
-constexpr int XCD_RUN = MPM_XCD_RUN;
-__device__ __forceinline__ int xcd_slice(int w, int n) {
-  int xcd = w & 7, idx = w >> 3;
-  int i = ((idx / XCD_RUN) * 8 + xcd) * XCD_RUN + (idx % XCD_RUN);
-  return i < n ? i : -1;
-}
-inline unsigned xcd_grid(int n) { return (unsigned)(((n + 8 * XCD_RUN - 1) / (8 * XCD_RUN)) * (8 * XCD_RUN)); }
 
 // Vertex forces without atomics: every element stores its corner forces f2, f3 (f1 = -(f2+f3), mpm_utils.py:
 // 168-170) and every vertex sums over its incident (element, corner) pairs through an ELL adjacency table that is

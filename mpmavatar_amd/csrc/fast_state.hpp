@@ -205,8 +205,6 @@ struct FastState {
   bool dist = false;  // multi-GPU: re-sorts only on request (all ranks re-sort together)
   bool dist_keep_cur = false;  // re-sort inside mpmhip_rccl_steps: the caller's mesh pointers are valid
   bool g2p_two_pass = false;   // k_g2p<., true, .>: see there (default: scenes without traditional particles)
-  int splat_first_max = 1 << 30;  // more splat workgroups than this go behind the chunk workgroups (MPMHIP_SPLAT_FIRST_MAX; measured
-                                  // neutral early and late -- profiles/r03_experiments.md -- so they stay in front)
   bool p2g_fixed_now = true, p2g_fixed_forced = false, mass_span_pending = false;  // the tile in use (decided per import from the mass span)
   float mass_span = 1.0f;
   float global_mass_span = 0.0f;  // sharded runs: the span over ALL ranks' simulated particles (mpmhip_dist_set_mass_span); 0: not set

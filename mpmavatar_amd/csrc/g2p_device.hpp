@@ -453,17 +453,15 @@ __device__ __forceinline__ void g2p2g_body(const ChunkRec *recs, int n_chunks, c
                                            float dt, const GridPtrs &g, const GridRead &rd, const SplatArgs &sa, const TradParams &tp,
                                            const GridParams &gp, const BCList &bcl, double *tile, int *esc, int &esc_n, float *red) {
   if (blockIdx.x == 0 && threadIdx.x == 0 && g.host_sig) post_host_flags(g);  // progress + flags of the substep before
-  if ((int)blockIdx.x >= sa.e0 && (int)blockIdx.x < sa.e0 + sa.n_extra) {  // splats of substep n + 1 (into W)
-    int e = (int)blockIdx.x - sa.e0;
-    if (e < sa.n_fbins) col_splat_wg<3>(tile, sa, e, d, g);
-    else if (e < sa.n_fbins + sa.n_mov_wg) mover_splat_wg(b, sa.js, e - sa.n_fbins, d, g);
-    return;
+  const LaunchLayout lay = layout_of(sa, n_chunks);
+  if (!wg_is_chunk((int)blockIdx.x, lay)) {
+    const WgRole role = wg_role((int)blockIdx.x, lay);
+    if (role.kind == WG_FACE) col_splat_wg<3>(tile, sa, role.index, d, g);  // splats of substep n + 1 (into W)
+    else if (role.kind == WG_JOINT) mover_splat_wg(b, sa.js, role.index, d, g);
+    else if (role.kind == WG_CLEAR) zero_blocks_wg(sa.z, role.index);  // clearing of Z
+    return;  // (no pack workgroups: the host takes this launch on one GPU only, g2p2g_ok)
   }
-  if ((int)blockIdx.x >= sa.z_first) {  // clearing of Z
-    zero_blocks_wg(sa.z, (int)blockIdx.x - sa.z_first);
-    return;
-  }
-  int w = xcd_slice((int)blockIdx.x - (sa.e0 == 0 ? sa.n_extra : 0), n_chunks);
+  const int w = wg_chunk((int)blockIdx.x, lay);
   if (w < 0) return;
   __builtin_amdgcn_s_setprio(3);
   const ChunkRec cm = recs[w];

@@ -29,13 +29,14 @@ __global__ void k_stress_trad(Bufs b, Dims d, mpmhip_model_scalars sc, float dt)
   st9(b.nv, N_STRESS, s, stress);
 }
 
-// The cloth scenes' stress launch with the collider splat's first pass in front (see col_splat_wg): workgroups [0, n_splat) splat,
-// the rest are k_stress_elem<true>.
+// The cloth scenes' stress launch with the collider splat's first pass in front (see col_splat_wg): workgroups [0, n_splat) are a
+// launch layout of riders alone -- the face bins and their padding -- and the rest are k_stress_elem<true>.
 __global__ __launch_bounds__(TPB) void k_stress_elem_splat(Bufs b, F3 *ef, Dims d, float friction_coeff, const int *face_slot,
                                                            const SortKey *skeys, int blk_bits, int n_splat, GridPtrs g, SplatArgs sa) {
   __shared__ double tile[4 * TILE_PAD];
   if ((int)blockIdx.x < n_splat) {
-    col_splat_wg<1>(tile, sa, (int)blockIdx.x, d, g);
+    const WgRole role = wg_role((int)blockIdx.x, launch_layout(sa.n_fbins, 0, 0, 0, 0));
+    if (role.kind == WG_FACE) col_splat_wg<1>(tile, sa, role.index, d, g);
     return;
   }
   stress_elem_body<true>(((int)blockIdx.x - n_splat) * (int)blockDim.x + (int)threadIdx.x, b, ef, d, friction_coeff, face_slot, skeys,
@@ -74,15 +75,17 @@ void launch_p2g(mpmhip_ctx *c, bool trad, bool jt, unsigned grid, int n_chunks, 
 #undef P2G_ARGS
 }
 // compute_stress_from_F_trial of the elements: mode 0 = from the stored directors (first substep after an import), 1 = with the
-// element finalize of the substep before fused in, 2 = the same with the collider splat's first pass in front (sa.n_fbins workgroups)
+// element finalize of the substep before fused in, 2 = the same with the collider splat's first pass in front (sa.n_fbins bins)
 void launch_stress_elem(mpmhip_ctx *c, int mode, const SplatArgs &sa) {
   FastState *f = c->fast;
   const Dims &d = f->d;
   const Bufs &b = f->buf[f->cur];
   hipStream_t s = c->stream;
-  if (mode == 2)
-    kstamp_launch(c, k_stress_elem_splat, nblk(d.n_e) + (unsigned)sa.n_fbins, TPB, b, f->eforce, d, c->sc.friction_coeff, f->face_slot,
-                  f->keys[1], f->blk_bits, sa.n_fbins, f->g, sa);
+  if (mode == 2) {
+    const unsigned n_splat = launch_layout(sa.n_fbins, 0, 0, 0, 0).grid();
+    kstamp_launch(c, k_stress_elem_splat, n_splat + nblk(d.n_e), TPB, b, f->eforce, d, c->sc.friction_coeff, f->face_slot, f->keys[1],
+                  f->blk_bits, (int)n_splat, f->g, sa);
+  }
   else if (mode == 1)
     kstamp_launch(c, k_stress_elem<true>, nblk(d.n_e), TPB, b, f->eforce, d, c->sc.friction_coeff, f->face_slot, f->keys[1], f->blk_bits,
                   f->g.counters, f->g.step_id);

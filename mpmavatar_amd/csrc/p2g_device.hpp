@@ -433,33 +433,32 @@ __device__ __forceinline__ void p2g_body(const ChunkRec *recs, int n_chunks, con
                                          int &esc_n, float *red, int bid) {
   WGT(g, 0, 0);
   if (bid == 0 && threadIdx.x == 0 && g.host_sig) post_host_flags(g);
-  // The splat workgroups go in front of the chunks (e0 = 0: the longest workgroups of the launch start first) or behind them
-  // (e0 = xcd_grid(n_chunks), MPMHIP_SPLAT_FIRST_MAX): measured the same to 1 % early and in the draped state, where ~740 of them
-  // take more than half of the first-round slots -- the dispatcher evens it out.
-  if (bid >= sa.e0 && bid < sa.e0 + sa.n_extra) {
-    int e = bid - sa.e0;
-    if (DBG(g, 256)) return;
-    if (e < sa.n_fbins) {   // (8192 / 16384: ablation switches)
-      if (DBG(g, 8192)) {}
-      else if (sa.splat_passes == 2) col_splat_wg<2>(tile, sa, e, d, g);   // (pass 0 rode in the stress launch)
-      else col_splat_wg<3>(tile, sa, e, d, g);
+  const LaunchLayout lay = layout_of(sa, n_chunks);
+  if (!wg_is_chunk(bid, lay)) {
+    const WgRole role = wg_role(bid, lay);
+    if (role.kind == WG_PACK) {  // (multi-GPU) halo pack, once everything in front has scattered
+      pack_wait(sa.pack, g.counters + CNT_LINK_TIMEOUT);
+      halo_pack_wg<true>(sa.pack.tb, g, role.index);
+      return;
     }
-    else if (e < sa.n_fbins + sa.n_mov_wg) { if (!DBG(g, 16384)) mover_splat_wg(b, sa.js, e - sa.n_fbins, d, g); }
+    if (role.kind == WG_CLEAR) {  // the clearing workgroups last: they fill the tail of the launch
+      if (!DBG(g, 2048)) zero_blocks_wg(sa.z, role.index);
+      WGT(g, 0, 6);
+      return;
+    }
+    // the riders, in front of the chunks
+    if (DBG(g, 256)) return;
+    if (role.kind == WG_FACE) {   // (8192 / 16384: ablation switches)
+      if (DBG(g, 8192)) {}
+      else if (sa.splat_passes == 2) col_splat_wg<2>(tile, sa, role.index, d, g);   // (pass 0 rode in the stress launch)
+      else col_splat_wg<3>(tile, sa, role.index, d, g);
+    }
+    else if (role.kind == WG_JOINT) { if (!DBG(g, 16384)) mover_splat_wg(b, sa.js, role.index, d, g); }
     WGT(g, 0, 6);
     wg_done(sa.pack);
     return;
   }
-  if (bid >= sa.z_first) {  // ... and the clearing workgroups last: they fill the tail of the launch
-    if (sa.pack.n_wg && bid >= sa.pack.first) {  // (multi-GPU) halo pack, once everything in front has scattered
-      pack_wait(sa.pack, g.counters + CNT_LINK_TIMEOUT);
-      halo_pack_wg<true>(sa.pack.tb, g, bid - sa.pack.first);
-      return;
-    }
-    if (!DBG(g, 2048)) zero_blocks_wg(sa.z, bid - sa.z_first);
-    WGT(g, 0, 6);
-    return;
-  }
-  int w = xcd_slice(bid - (sa.e0 == 0 ? sa.n_extra : 0), n_chunks);
+  const int w = wg_chunk(bid, lay);
   if (w < 0) { wg_done(sa.pack); return; }
   if (g.stagger > 0 && bid < g.stagger_first) {
     // The workgroups of the first round all start within a microsecond, load together and then scatter together: memory

@@ -100,7 +100,7 @@ __device__ __forceinline__ void mover_escaped(V3 x, V3 pv, const Dims &d, const 
 }
 
 // The two splats are small, latency-bound and independent of the particle transfer, so they ride along in the p2g
-// LAUNCH as extra workgroups (k_p2g: blockIdx < n_extra) instead of being kernels of their own: as separate launches
+// LAUNCH as extra workgroups (k_p2g: wg_role, launch_layout.hpp) instead of being kernels of their own: as separate launches
 // they either sit on the critical path (17 us) or, on a side stream, cost two cross-queue barrier packets per
 // substep (~6 us of idle GPU each, measured with rocprofv3 --kernel-trace).
 struct SplatArgs {
@@ -112,12 +112,20 @@ struct SplatArgs {
   int splat_passes;        // 3: both passes of the body-face splat here; 2: only the normal pass (pass 0 rode in the stress launch)
   JointSplatArgs js;       // workgroups [n_fbins, n_fbins + n_mov_wg): joints
   int n_mov_wg;
-  int n_extra;             // n_fbins + n_mov_wg rounded up to a multiple of 8 (keeps the XCD mapping of the chunks)
-  int e0;                  // first workgroup of the splats: 0 (in front of the chunks) or xcd_grid(n_chunks) (behind them)
+  int n_extra;             // LaunchLayout::n_riders
   ZeroArgs z;              // workgroups [z_first, z_first + z.n_wg), after the chunk workgroups: clear the other
   int z_first;             // accumulator buffer
   PackArgs pack;           // workgroups [pack.first, ...) after those: multi-GPU halo pack (see PackArgs)
 };
+// Where each kind of workgroup begins is LaunchLayout's arithmetic (launch_layout.hpp) and nobody else's: the host copies a layout in,
+// the kernels read it back for wg_role.  (z.n_wg and pack.n_wg are the host's inputs to the layout and stay the caller's.)
+inline void set_layout(SplatArgs &sa, const LaunchLayout &L) {
+  sa.n_fbins = L.n_fbins; sa.n_mov_wg = L.n_joint; sa.n_extra = L.n_riders;
+  sa.z_first = L.z_first; sa.pack.first = L.pack_first;
+}
+__device__ __forceinline__ LaunchLayout layout_of(const SplatArgs &sa, int n_chunks) {
+  return LaunchLayout{sa.n_fbins, sa.n_mov_wg, sa.n_extra, n_chunks, sa.z_first, sa.pack.first, sa.pack.n_wg};
+}
 
 // ---- body-face splat: the pieces the three forms share ----
 // The two tile layouts: node (i, j, k) of channel c at c * CS + i * SI + j * SJ + k.
