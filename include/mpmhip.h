@@ -468,6 +468,50 @@ int mpmhip_nn_dist2(int32_t device, void *stream, const float *src, int32_t n_sr
 int mpmhip_geo_reduce(int32_t device, void *stream, const float *dist2_12, int32_t n1, const float *dist2_21, int32_t n2,
                       double tau, double *scratch, double *out);
 
+/* ---- after the solver: the ambient-occlusion bake ---------------------------------------------------------------------
+ * What the reference runs as a Blender subprocess per frame (train_material_params.py:819-822 calls blender/bake.py, which bakes
+ * type AO with Cycles into aomap/NNN.png, bake.py:37-78): the [map_h*map_w] AO map of the UV mesh, from vertices that are already
+ * on the device.  The definition (coverage, texel frame, direction table, any-hit occlusion, margin) is csrc/ao_math.hpp and
+ * DESIGN.md section 19; Cycles' own sampling cannot be inspected, so that definition is this project's.  Stand-alone maps on [dev]
+ * arrays; nothing here allocates or synchronises.  Scratch is the caller's: the arrays then live and die with the caller's tensors
+ * under its allocator's stream rules, and the library keeps no state to destroy.  All arithmetic per frame is fp32, no
+ * floating-point atomics, integer atomics only in the grid's count and fill: the same input gives the same bits.
+ * All return MPMHIP_ERR_INVALID, with nothing launched, for a negative count, a non-positive map size, map_h * map_w > 2^31 - 1,
+ * samples outside [1, 4096], a scratch that is too small or a NULL required pointer.  Indices are the caller's to check.
+ *
+ * mpmhip_ao_coverage (once per mesh; replaces the UV rasterisation inside bake.py:73): cov_face [map_h*map_w] = the lowest face
+ * whose UV triangle (vt [n_vt*2] through ft [n_faces*3], the 'vt' and 'f v/vt' lines) contains the texel centre
+ * u = (x + 0.5) / W, v = 1 - (y + 0.5) / H, edges inclusive, both windings, -1 = none; cov_bary [map_h*map_w*2] = the weights of
+ * the face's second and third corner, float64 rounded once.  A face without UV area or with a repeated vertex covers nothing. */
+int mpmhip_ao_coverage(int32_t device, void *stream, const int32_t *faces, const int32_t *ft, int32_t n_faces, const float *vt,
+                       int32_t n_vt, int32_t map_h, int32_t map_w, int32_t *cov_face, float *cov_bary);
+/* bytes of scratch that mpmhip_ao_build_grid and mpmhip_ao_trace share for a mesh of n_faces faces, a grid of at most cap_cells
+ * cells and at most cap_entries (cell, face) entries. */
+int mpmhip_ao_scratch_bytes(int32_t device, int32_t n_faces, int32_t cap_cells, int32_t cap_entries, int64_t *out_bytes);
+/* The per-texel frame the rays leave from (inspection; the trace computes the same values itself): origin, normal, tangent
+ * [map_h*map_w*3] each, zeros on texels that no face covers or whose face has no area in this frame.  rot [map_h*map_w*2] is the
+ * per-texel (cos, sin) table. */
+int mpmhip_ao_texel_frames(int32_t device, void *stream, const float *verts, const int32_t *faces, int32_t n_faces, int32_t map_h,
+                           int32_t map_w, const int32_t *cov_face, const float *cov_bary, const float *rot, float *origin,
+                           float *normal, float *tangent);
+/* Per frame, stage 1 (bake.py:50, the import of uvmesh/NNN.obj, and Cycles' own BVH build): one 48-byte record (v0, e1, e2) per
+ * face, the mesh's bounding box, and a uniform grid over it (cells of about twice the mean edge, at most cap_cells) as
+ * count / exclusive scan / fill, all in scratch. */
+int mpmhip_ao_build_grid(int32_t device, void *stream, const float *verts, const int32_t *faces, int32_t n_faces, int32_t cap_cells,
+                         int32_t cap_entries, void *scratch, int64_t scratch_bytes);
+/* Per frame, stage 2 (bake.py:73, bpy.ops.object.bake(type='AO')): ao [map_h*map_w] = 1 - occluded / samples on the n_cov texels
+ * of cov_list (the covered ones, compacted once); other texels are not written.  dirs [samples*3] is the direction table.  A ray
+ * is occluded when it meets any face but the texel's own with bias < t <= max_distance.  If the frame's grid needed more than
+ * cap_entries entries every texel of cov_list is NaN: loud in the image, no access out of bounds. */
+int mpmhip_ao_trace(int32_t device, void *stream, const float *verts, const int32_t *faces, int32_t n_faces, const int32_t *cov_face,
+                    const float *cov_bary, const int32_t *cov_list, int32_t n_cov, const float *rot, const float *dirs,
+                    int32_t samples, float bias, float max_distance, int32_t cap_cells, int32_t cap_entries, void *scratch,
+                    int64_t scratch_bytes, float *ao);
+/* Per frame, stage 3, one margin pixel (bake.py:37, bake.margin = ao_res // 256): a texel with in_mask = 0 and covered texels
+ * among its 8 neighbours takes their mean (row-major order) and out_mask = 1; in and out must not overlap. */
+int mpmhip_ao_margin(int32_t device, void *stream, int32_t map_h, int32_t map_w, const float *in_val, const uint8_t *in_mask,
+                     float *out_val, uint8_t *out_mask);
+
 /* ---- after the solver: the Gaussian rasteriser ----------------------------------------------------------------------
  * What the reference calls as diff_gauss.GaussianRasterizer (gaussian_renderer/__init__.py:14,36-103; the extension is not
  * vendored there, README.md:51): the published 3D Gaussian splatting forward pass, as the eval loop

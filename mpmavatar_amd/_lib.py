@@ -115,6 +115,13 @@ SIGNATURES = {
     "mpmhip_mesh_sample": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp]),
     "mpmhip_nn_dist2": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp]),
     "mpmhip_geo_reduce": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_double, vp, vp]),
+    "mpmhip_ao_coverage": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
+    "mpmhip_ao_scratch_bytes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "mpmhip_ao_texel_frames": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 6),
+    "mpmhip_ao_build_grid": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64]),
+    "mpmhip_ao_trace": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_float, C.c_float,
+                                  C.c_int32, C.c_int32, vp, C.c_int64, vp]),
+    "mpmhip_ao_margin": (C.c_int, [C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp]),
     "mpmhip_raster_create": (C.c_int, [C.c_int32, vp, C.POINTER(vp)]),
     "mpmhip_raster_destroy": (None, [vp]),
     "mpmhip_raster_forward": (C.c_int, [vp, C.POINTER(RasterSettings), C.c_int32, vp, vp, C.c_int32] + [vp] * 8),

@@ -2,7 +2,8 @@
 consumes the same files: per-frame ``uvmesh/NNN.obj`` (train_material_params.py:776-822, run_demo.py:500-545),
 ``read_obj`` (utils/general_utils.py:318-334), ``split_idx.npz`` (preprocess/split_garments.py:84-94) and the
 ``best_param_*.npz`` / ``last_param_*.npz`` checkpoints (train_material_params.py:145-148,725-728).  Host-side Python,
-like the reference.  The Blender AO bake and the diff_gauss rasteriser that consume these files are out of scope."""
+like the reference.  The AO bake that consumed uvmesh/NNN.obj in the reference runs on the device here (ao_bake.py, which parses the
+same UV template); write_png is what it and the rasteriser's callers write their images with."""
 from __future__ import annotations
 
 import os

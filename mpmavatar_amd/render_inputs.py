@@ -6,7 +6,7 @@ poses the Gaussians and renders (train_material_params.py:819-845, run_demo.py:5
 needed: ``MeshFrames.set_mesh_by_verts`` takes the solver's ``particle_x`` as it lies in HBM, and ``BoundGaussians.render_inputs``
 returns exactly ``means3D, means2D, opacities, scales, rotations`` (+ the caller's ``shs`` / ``colors_precomp`` and the ``extra``
 primitives concatenated behind, :84-91) in one launch (``mpmhip_render_inputs``).  The rasteriser they go to is
-``mpmavatar_amd/rasterizer.py``; the AO bake stays out of scope, and the OBJ files are still what Blender needs (``io_formats.write_uv_obj``), but nothing has to be read back from them.
+``mpmavatar_amd/rasterizer.py``; the AO bake is ``mpmavatar_amd/ao_bake.py``, from the same vertices on the device, so the OBJ files (``io_formats.UVMeshWriter``) are needed only by a caller who still wants Blender's bake.
 
     frames = MeshFrames(faces);  frames.set_mesh_by_verts(sim2wld(state.particle_x[n_e + n_t:]))
     args = gaussians.render_inputs(frames, override_color=colors, extra=(xyz, colors, opacity, scales, rotations))
