@@ -428,6 +428,48 @@ int mpmhip_gauss_reg_backward(int32_t device, void *stream, int32_t n, const flo
                               const int32_t *radii, const uint8_t *visible, float threshold_xyz, float threshold_scale,
                               const int32_t *n_visible, const float *g_terms, float *d_opacity, float *d_xyz, float *d_scaling);
 
+/* ---- densification of the bound Gaussians (scene/gaussian_model.py:378-526, train_appearance.py:245-257) ----------------------------
+ * The last block of the appearance loop: the statistics of every iteration, densify_and_prune (clone, split, prune, the face rule
+ * of prune_points :379-385) and reset_opacity (:284-287).  Stand-alone maps on [dev] arrays; nothing allocates or synchronises;
+ * fp32; integer atomics only: the same input gives the same bits.
+ *
+ * mpmhip_densify_stats_add (add_densification_stats :524-526 and train_appearance.py:248), in place, one launch: for rows with
+ * radii[i] > 0 (the rasteriser's int32 radii) or visible[i] != 0 (a byte mask, counted as radius 1; exactly one of the two pointers
+ * is given)  xyz_gradient_accum[i] += sqrt(gx^2 + gy^2) of viewspace_grad [n*3],  denom[i] += 1,  max_radii2D[i] = max(., radii[i]). */
+int mpmhip_densify_stats_add(int32_t device, void *stream, int32_t n, const float *viewspace_grad, const int32_t *radii,
+                             const uint8_t *visible, float *xyz_gradient_accum, float *denom, float *max_radii2D);
+/* densify_and_prune (:508-522 with densify_and_clone :488-506, densify_and_split :453-486, prune_points :378-405) in two calls with
+ * the caller's one read-back between them.  With g = accum / denom (NaN -> 0) and gs = exp(scaling[i]) * face_scaling[binding[i]]:
+ * clone when g >= max_grad and max(gs) <= dense_limit, split when g >= max_grad and max(gs) > dense_limit (two children, the source
+ * leaves); then, over the enlarged set, a row is flagged when sigmoid(opacity) < min_opacity or, with prune_big != 0, when its
+ * max world scale > world_limit (the reference's screen-size test is dead: densification_postfix zeroes max_radii2D before it is
+ * read, so a screen size only switches the world-size test on); flagged rows leave unless that empties their face.
+ * mpmhip_densify_plan decides and leaves out_counts [MPMHIP_DENSIFY_COUNTS] int32 on the device: n_out, n_cloned, n_split (selected),
+ * n_pruned (rows the last prune removed), an error flag (a binding outside [0, n_faces); such a row reads nothing), and the rows at
+ * which the clones, the first children and the second children begin.  scratch: mpmhip_densify_scratch_bytes(n, n_faces) bytes,
+ * handed unchanged to mpmhip_densify_emit.  MPMHIP_ERR_INVALID: a negative count, 3 n + 1 > 2^31 - 1, a required pointer NULL, a
+ * scratch that is too small. */
+#define MPMHIP_DENSIFY_COUNTS 8
+#define MPMHIP_DENSIFY_MAX_TENSORS 24
+int mpmhip_densify_scratch_bytes(int32_t device, int32_t n, int32_t n_faces, int64_t *out_bytes);
+int mpmhip_densify_plan(int32_t device, void *stream, int32_t n, int32_t n_faces, const float *scaling, const float *opacity,
+                        const int32_t *binding, const float *face_scaling, const float *xyz_gradient_accum, const float *denom,
+                        float max_grad, float dense_limit, float min_opacity, float world_limit, int32_t prune_big, void *scratch,
+                        int64_t scratch_bytes, int32_t *out_counts);
+/* mpmhip_densify_emit writes the n_out rows the plan counted, in the reference's order [kept originals | clones | first children |
+ * second children], each block in source order: out_src (the source row), out_kind (0 kept, 1 clone, 2 split child), out_binding,
+ * out_binding_counter [n_faces] (the new per-face count), and the n_tensors <= MPMHIP_DENSIFY_MAX_TENSORS row-aligned fp32 tensors
+ * named by the HOST arrays in / out / widths (floats per row, > 0) / modes: 0 copied, 1 copied for kept rows and zero for new ones
+ * (Adam moments), 2 the _xyz and 3 the _scaling of the model (width 3), which a child computes as
+ *   xyz = R(rotation[i] / |rotation[i]|) (gs * noise[i, c]) + xyz[i],   scaling = log((gs / face_scaling) / 1.6)
+ * with noise [n*2*3] standard normals (build_rotation: utils/general_utils.py:116-137).  One gather launch for all tensors. */
+int mpmhip_densify_emit(int32_t device, void *stream, int32_t n, int32_t n_faces, int32_t n_out, const float *xyz, const float *scaling,
+                        const float *rotation, const int32_t *binding, const float *face_scaling, const float *noise, const void *scratch,
+                        int64_t scratch_bytes, int32_t n_tensors, const float *const *in, float *const *out, const int32_t *widths,
+                        const int32_t *modes, int32_t *out_src, int32_t *out_kind, int32_t *out_binding, int32_t *out_binding_counter);
+/* reset_opacity (:284-287): out[i] = log(x / (1 - x)), x = min(sigmoid(opacity[i]), 0.01). */
+int mpmhip_reset_opacity(int32_t device, void *stream, int64_t n, const float *opacity, float *out);
+
 /* MPMWARP.export_particle_cov_to_torch (warp_mpm/mpm_solver.py:543-561) = kernel compute_cov_from_F
  * (warp_mpm/mpm_utils.py:1108-1132): new_cov[6p..] = upper triangle (xx xy xz yy yz zz) of F_trial[p] * sym(particle_cov[6p..])
  * * F_trial[p]^T for p < n (= n_particles - n_vertices).  Stand-alone map on [dev] arrays in the reference's AoS layout. */

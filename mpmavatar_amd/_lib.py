@@ -111,6 +111,11 @@ SIGNATURES = {
     "mpmhip_mesh_reg_backward": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32] + [vp] * 9),
     "mpmhip_gauss_reg_forward": (C.c_int, [C.c_int32, vp, C.c_int32] + [vp] * 5 + [C.c_float, C.c_float] + [vp] * 3),
     "mpmhip_gauss_reg_backward": (C.c_int, [C.c_int32, vp, C.c_int32] + [vp] * 5 + [C.c_float, C.c_float] + [vp] * 5),
+    "mpmhip_densify_stats_add": (C.c_int, [C.c_int32, vp, C.c_int32] + [vp] * 6),
+    "mpmhip_densify_scratch_bytes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "mpmhip_densify_plan": (C.c_int, [C.c_int32, vp, C.c_int32, C.c_int32] + [vp] * 6 + [C.c_float] * 4 + [C.c_int32, vp, C.c_int64, vp]),
+    "mpmhip_densify_emit": (C.c_int, [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 7 + [C.c_int64, C.c_int32] + [vp] * 8),
+    "mpmhip_reset_opacity": (C.c_int, [C.c_int32, vp, C.c_int64, vp, vp]),
     "mpmhip_face_areas":(C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, vp]),
     "mpmhip_mesh_sample": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp]),
     "mpmhip_nn_dist2": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp]),
