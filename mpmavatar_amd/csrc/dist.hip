@@ -6,20 +6,6 @@ namespace mpm {
 
 namespace {
 
-// compaction of the flagged blocks onto a list; thread 0 also files the total (rc[slot], overflow bit) and every thread
-// clears its share of `clear` (the ranges table k_ranges fills next) -- both used to be launches of their own
-__global__ void k_compact(const int *flag, const int *index, int n, int *list, int cap, int *rc, int slot, int over_bit, int *clear,
-                          int n_clear) {
-  int b = blockIdx.x * blockDim.x + threadIdx.x;
-  for (int i = b; i < n_clear; i += (int)(gridDim.x * blockDim.x)) clear[i] = 0;
-  if (b == 0 && rc) {
-    int tot = index[n - 1] + flag[n - 1];
-    rc[slot] = tot;
-    if (tot > cap) atomicOr(rc + RC_OVER, over_bit);
-  }
-  if (b < n && flag[b] && index[b] < cap) list[index[b]] = b;
-}
-
 __global__ void k_link_ping(unsigned *data, int n, int *cnt, int *flag, int seq) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) data[i] = link_pattern(seq, i);
   link_signal(cnt, gridDim.x, flag, seq);
@@ -489,15 +475,16 @@ static int rccl_rebin(mpmhip_ctx *c) {
   f->peers.clear();
   for (auto &p : f->rpeers) {
     hipLaunchKernelGGL(k_shared_flags, nblk(nb), TPB, 0, s, mine, f->map_all + (size_t)p.rank * f->nblocks, nb, p.flag);
-    if ((rc = scan_flags(c, p.flag, p.index, nb, &p.n_blocks))) return rc;
+    // index[] and blocks[] in one go (the re-sort's flag compaction), total read back; too many for blocks[]: grown, and again
+    if ((rc = compact_shared_blocks(c, p.flag, nb, p.index, p.blocks, p.cap_blocks, &p.n_blocks))) return rc;
     if (p.n_blocks > p.cap_blocks) {
       int cap = std::max(p.n_blocks + p.n_blocks / 2, 256);
       if ((rc = dalloc(c, &p.blocks, (size_t)cap, false))) return rc;
       if ((rc = dalloc(c, &p.halo_send, halo_floats(cap, HALO_CHANNELS_MAX), false))) return rc;   // (sized for the wider record)
       if ((rc = dalloc(c, &p.halo_recv, halo_floats(cap, HALO_CHANNELS_MAX), false))) return rc;
       p.cap_blocks = cap;
+      if ((rc = compact_shared_blocks(c, p.flag, nb, p.index, p.blocks, p.cap_blocks, nullptr))) return rc;
     }
-    if (p.n_blocks) hipLaunchKernelGGL(k_compact, nblk(nb), TPB, 0, s, p.flag, p.index, nb, p.blocks, p.cap_blocks, (int *)nullptr, 0, 0, (int *)nullptr, 0);
   }
   if (f->link_want && !f->link_decided && (rc = rccl_link_setup(c))) return rc;   // (first re-sort: the links come up here)
   for (auto &p : f->rpeers) f->peers.push_back(p.view());

@@ -342,26 +342,11 @@ int fast_init(mpmhip_ctx *c) {
   if ((rc = dalloc(c, &f->inv, (size_t)d.n_p))) return rc;
   if ((rc = dalloc(c, &f->face_slot, (size_t)3 * d.n_e))) return rc;
   if ((rc = dalloc(c, &f->eforce, (size_t)3 * d.n_e + 1))) return rc;
-  if ((rc = dalloc(c, &f->adj_cnt, (size_t)d.n_v + 1))) return rc;
-  if ((rc = dalloc(c, &f->order, (size_t)d.n_p))) return rc;
-  if ((rc = dalloc(c, &f->iota, (size_t)d.n_p))) return rc;
   if ((rc = f->acc.allocate(c, &f->g, f->nblocks, d.n_e == 0 && d.n_v == 0 && d.n_t > 0))) return rc;
   if ((rc = dalloc(c, &f->g.vout, f->nblocks * GCH_VOUT * 64))) return rc;
   if ((rc = dalloc(c, &f->g.counters, CNT_N))) return rc;
   if ((rc = dalloc(c, &f->pack_done, (size_t)DONE_SHARDS * DONE_STRIDE))) return rc;
-  // one allocation, one memset per re-sort: [particle-block flags | active-block flags | device counts]
-  static_assert(RC_N <= 64, "device counts of a re-sort");
-  f->fc_tiles = (int)((f->nblocks + FC_TILE - 1) / FC_TILE);
-  f->fc_groups = (f->fc_tiles + FC_GROUP - 1) / FC_GROUP;
-  f->n_clear = (int)(2 * f->nblocks + 64 + 2 * f->fc_groups);
-  if ((rc = dalloc(c, &f->pb_flag, (size_t)f->n_clear + 2 * f->fc_tiles))) return rc;
-  f->ab_flag = f->pb_flag + f->nblocks;
-  f->rcnt = f->pb_flag + 2 * f->nblocks;
-  f->fc_gsum = f->rcnt + 64;
-  f->fc_tcount = f->fc_gsum + 2 * f->fc_groups;
-  if ((rc = dalloc(c, &f->pb_index, f->nblocks))) return rc;
-  if ((rc = dalloc(c, &f->ab_index, f->nblocks))) return rc;
-  f->g.ab_flag = f->ab_flag;
+  if ((rc = resort_alloc(c))) return rc;
   MPM_HIP_CHECK(c, hipHostMalloc((void **)&f->h_pin, PIN_N * sizeof(int), hipHostMallocDefault));
   int *hs = nullptr, *ds = nullptr;
   MPM_HIP_CHECK(c, hipHostMalloc((void **)&hs, SIG_WORDS * sizeof(int), hipHostMallocMapped));
@@ -383,7 +368,7 @@ void fast_destroy(mpmhip_ctx *c) {
   for (void *p : f->allocs) (void)hipFree(p);
   if (f->h_pin) (void)hipHostFree(f->h_pin);
   if (f->h_sig) (void)hipHostFree((void *)f->h_sig);
-  f->h_ranges.release(); f->h_plist.release(); f->h_chunks.release(); f->h_chunks_g.release();
+  resort_free(f);
   delete f;
   c->fast = nullptr;
 }
@@ -394,14 +379,8 @@ int fast_add_collider_storage(mpmhip_ctx *c, MeshCollider &mc) {
     mc.weight = c->colliders[0].weight;
     return MPMHIP_OK;
   }
-  int rc, nf = c->num_mesh_f;
-  for (int i = 0; i < 2; ++i)
-    if ((rc = dalloc(c, &f->fkeys[i], (size_t)nf))) return rc;
-  if ((rc = dalloc(c, &f->forder, (size_t)nf))) return rc;
-  if ((rc = dalloc(c, &f->fidx, (size_t)3 * nf))) return rc;
-  if ((rc = dalloc(c, &f->fiota, (size_t)nf))) return rc;
-  if ((rc = dalloc(c, &f->fb_start, f->nblocks))) return rc;
-  if ((rc = dalloc(c, &f->fb_cnt, f->nblocks))) return rc;
+  int rc;
+  if ((rc = resort_alloc_face_sort(c, c->num_mesh_f))) return rc;
   return f->acc.add_collider_channels(c, &mc.weight);
 }
 

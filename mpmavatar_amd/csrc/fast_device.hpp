@@ -16,7 +16,6 @@
 #include <thread>
 
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include "bc.hpp"
 #include "ctx.hpp"
@@ -170,7 +169,7 @@ __device__ __forceinline__ int kf_blk(int kf) { return kf & 255; }
 __device__ __forceinline__ int kf_cell(int kf) { return kf >> 8; }
 __device__ __forceinline__ int key_block(SortKey k, int kf) { return (int)((k >> kf_cell(kf)) & ((1u << kf_blk(kf)) - 1u)); }
 __device__ __forceinline__ int key_state(SortKey k, int kf) { return (int)((k >> (kf_blk(kf) + kf_cell(kf))) & 3u); }
-__device__ __forceinline__ bool key_inactive(SortKey k, int blk_bits) { return key_state(k, blk_bits) >= 2; }
+__device__ __forceinline__ bool key_inactive(SortKey k, int kf) { return key_state(k, kf) >= 2; }
 __device__ __forceinline__ SortKey make_key(V3 x, V3 v, float lead, int cls, int state, const Dims &d, int kf) {
   int bb = kf_blk(kf), cb = kf_cell(kf);
   int cx = (int)(x.x * d.inv_dx - 0.5f), cy = (int)(x.y * d.inv_dx - 0.5f), cz = (int)(x.z * d.inv_dx - 0.5f);
@@ -226,15 +225,45 @@ __device__ __forceinline__ unsigned long long rs_peers(int dg) {
   return peers;
 }
 
+// One slice of a tile counted into the tile's digit histogram h[RS_BINS] (LDS): one atomic per run of lanes with the same digit.
+// dg == RS_BINS where the lane holds no pair (in == false).
+__device__ __forceinline__ void rs_count_digit(int *h, int dg, bool in, int lane) {
+  unsigned long long peers = rs_peers(dg);
+  if (in && (peers & ((1ull << lane) - 1)) == 0) atomicAdd(&h[dg], __popcll(peers));
+}
+// ... and the finished h[] filed as the tile's row of hist and into its group's sums (thread t = digit t)
+__device__ __forceinline__ void rs_file_hist(const int *h, unsigned tile, int t, int *hist, int *gsum) {
+  int v = h[t];
+  hist[(size_t)tile * RS_BINS + t] = v;
+  if (v) atomicAdd(gsum + (size_t)(tile / RS_GROUP) * RS_BINS + t, v);
+}
+
+// Exclusive offset of this thread's v among the 256 threads of its workgroup: shuffle scan inside the wavefront, then the totals of
+// the wavefronts in front (ws: 4 ints of LDS).  Has a barrier in it: every thread of the workgroup calls it.
+__device__ __forceinline__ int wg256_exclusive(int v, int *ws) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    int a = __shfl_up(inc, o);
+    if (lane >= o) inc += a;
+  }
+  if (lane == 63) ws[wv] = inc;
+  __syncthreads();
+  return inc - v + (wv > 0 ? ws[0] : 0) + (wv > 1 ? ws[1] : 0) + (wv > 2 ? ws[2] : 0);
+}
+
 // rc: re-sort counts kept on the device so that the table kernels can be enqueued back to back without a host round trip
 // (the host reads them once, at the end): [0] particle blocks, [1] active blocks, [2] chunks, [3] chunks incl. ghost copies,
-// [4] any ghost copy, [5] capacity overflow bits (1 plist / ranges, 2 alist, 4 chunk records, 8 face bins), [6] face bins
-enum { RC_NP = 0, RC_NA = 1, RC_NCH = 2, RC_NCHG = 3, RC_GHOST = 4, RC_OVER = 5, RC_NFB = 6, RC_N = 8 };
+// [4] any ghost copy, [5] capacity overflow bits (RC_OVER_*), [6] face bins, [7] blocks shared with one peer (sharded runs: filed
+// after the re-sort, once per peer)
+enum { RC_NP = 0, RC_NA = 1, RC_NCH = 2, RC_NCHG = 3, RC_GHOST = 4, RC_OVER = 5, RC_NFB = 6, RC_NSHARED = 7, RC_N = 8 };
+enum { RC_OVER_P = 1, RC_OVER_A = 2, RC_OVER_CHUNKS = 4, RC_OVER_FBINS = 8 };  // too small: plist / ranges, alist, chunk records, face bins
 
-// The same compaction without a scan launch in front (the re-sort's two block lists; rocPRIM's scan is two launches): k_flag_count
-// files the flagged blocks per tile of FC_TILE flags and per group of FC_GROUP tiles, k_compact_tiles works out every tile's start
-// from those (uniform loads: <= groups + FC_GROUP scalars) and scans inside the tile.  index[] is filled as the exclusive scan
-// would have filled it.
+// Compaction of block flags onto a list without a scan launch in front (rocPRIM's scan is two launches): k_flag_count files the
+// flagged blocks per tile of FC_TILE flags and per group of FC_GROUP tiles, k_compact_tiles works out every tile's start from those
+// (uniform loads: <= groups + FC_GROUP scalars) and scans inside the tile.  index[] is filled as an exclusive scan would have filled
+// it.  The re-sort's two block lists and the shared-block lists of the sharded loop (resort.hip compact_flags).
 constexpr int FC_TILE = 1024, FC_GROUP = 16;
 
 // ------------------------------------------------------------------------------------------------

@@ -5,7 +5,6 @@
 
 namespace mpm {
 
-
 // ================================================================================================
 // host side
 // ================================================================================================
@@ -101,21 +100,20 @@ inline int *link_flag(float *arena, int par) { return (int *)arena + par * LINK_
 // Pinned host scratch (FastState::h_pin): where the read-backs behind the host's waits land.  One name per slot; a block is
 // [first, first + its _N).  The slots are laid out one after the other, so no two can share a word; the assert keeps that true
 // if one is ever placed by hand.
-constexpr int PIN_SCAN_N = 2, PIN_STATS_N = CNT_STATS_N, PIN_RCNT_N = RC_N, PIN_MASS_N = 3;
+constexpr int PIN_STATS_N = CNT_STATS_N, PIN_RCNT_N = RC_N, PIN_MASS_N = 3;
 enum {
-  PIN_SCAN = 0,                          // scan_flags: the two addends of the total
-  PIN_STATS = PIN_SCAN + PIN_SCAN_N,     // fast_stats: the first CNT_STATS_N device counters
+  PIN_STATS = 0,                         // fast_stats: the first CNT_STATS_N device counters
   PIN_ADJ_K = PIN_STATS + PIN_STATS_N,   // do_import: width of the vertex adjacency
   PIN_DIST_DRIFT,                        // fast_dist_drift_flag: this rank's CNT_DRIFT
   PIN_LINK_VOTE,                         // rccl_link_setup: CNT_LINK_VOTE_ALL
   PIN_LINK_TIMEOUT,                      // fast_rccl_steps: CNT_LINK_TIMEOUT
   PIN_HALO_MULTI,                        // rccl_rebin: a block shared with more than one peer (no fused halo)
   PIN_BODY_MOVES,                        // fast_body_at_rest_begin: CNT_BODY_MOVES
-  PIN_RCNT,                              // rebin: the counts of the re-sort (RC_*)
+  PIN_RCNT,                              // rebin, compact_shared_blocks: the counts of the re-sort (RC_*)
   PIN_MASS = PIN_RCNT + PIN_RCNT_N,      // rebin: CNT_MMIN, CNT_MMAX, CNT_NSEL
   PIN_N = PIN_MASS + PIN_MASS_N
 };
-static_assert(PIN_SCAN + PIN_SCAN_N <= PIN_STATS && PIN_STATS + PIN_STATS_N <= PIN_ADJ_K && PIN_ADJ_K < PIN_DIST_DRIFT &&
+static_assert(PIN_STATS + PIN_STATS_N <= PIN_ADJ_K && PIN_ADJ_K < PIN_DIST_DRIFT &&
               PIN_BODY_MOVES < PIN_RCNT && PIN_RCNT + PIN_RCNT_N <= PIN_MASS && PIN_MASS + PIN_MASS_N <= PIN_N,
               "blocks of the pinned scratch overlap");
 
@@ -187,6 +185,8 @@ class AccumRing {
   int fused_read = -1, fused_col = 0, fused_mov = 0;  // buffer the last fused launch read: cleared by the next one (or clear_fused_read)
 };
 
+struct ResortState;
+
 struct FastState {
   Rccl rccl;
   std::vector<RcclPeer> rpeers;
@@ -205,10 +205,9 @@ struct FastState {
   bool dist = false;  // multi-GPU: re-sorts only on request (all ranks re-sort together)
   bool dist_keep_cur = false;  // re-sort inside mpmhip_rccl_steps: the caller's mesh pointers are valid
   bool g2p_two_pass = false;   // k_g2p<., true, .>: see there (default: scenes without traditional particles)
-  bool p2g_fixed_now = true, p2g_fixed_forced = false, mass_span_pending = false;  // the tile in use (decided per import from the mass span)
-  float mass_span = 1.0f;
-  float global_mass_span = 0.0f;  // sharded runs: the span over ALL ranks' simulated particles (mpmhip_dist_set_mass_span); 0: not set
   bool p2g_fixed = true;       // p2g's chunk tile in packed fixed point (k_p2g<.., FX = true>); MPMHIP_P2G_TILE=f64: the fp64 tile
+  bool p2g_fixed_forced = false;  // ... whatever the mass span (MPMHIP_P2G_TILE=fx)
+  float global_mass_span = 0.0f;  // sharded runs: the span over ALL ranks' simulated particles (mpmhip_dist_set_mass_span); 0: not set
   // adaptive collective re-sorts (mpmhip_rccl_steps with rebin_interval <= 0): the ranks' drift flags are max-reduced
   // every DIST_POLL substeps and read DIST_LAG substeps later, so every rank takes the same decision at the same substep
   int dist_since = 0;
@@ -223,79 +222,40 @@ struct FastState {
   float last_dt = 0.0f;
   int true_since_rebin = 0;        // substeps since the last re-sort (steps_since_rebin is overwritten to force one)
   size_t nblocks = 0;
-  Bufs buf[2]{};
-  int cur = 0;
-  int *perm[2] = {nullptr, nullptr}, *inv = nullptr, *face_slot = nullptr;
-  // body-face bins (collider gather)
-  unsigned *fkeys[2] = {nullptr, nullptr};
-  int *forder = nullptr, *fiota = nullptr, *fb_start = nullptr, *fb_cnt = nullptr;
-  bool faces_binned = false;
-  int rebins_since_face_sort = 0;
-  FaceBin *fbins = nullptr;
-  int *fidx = nullptr;  // [n_f][3] face vertex ids in bin order
-  int cap_fbins = 0, n_fbins = 0;
   F3 *eforce = nullptr;  // [3][n_e] + zero slot
-  int *adj_cnt = nullptr, *adj_o = nullptr, *adj_s = nullptr;
-  int adj_K = 0, adj_cap = 0;
   VAdj va() const { return VAdj{adj_s, eforce, adj_K, d.n_v, d.n_e}; }
-  SortKey *keys[2] = {nullptr, nullptr};
-  int *order = nullptr, *iota = nullptr;
-  void *sort_tmp = nullptr, *scan_tmp = nullptr;
-  size_t sort_tmp_bytes = 0, scan_tmp_bytes = 0;
-  int *rs_hist = nullptr;      // [tiles][RS_BINS] digit counts of the radix sort (see k_rs_hist)
-  int rs_tiles = 0;
-  int *rs_gsum = nullptr;      // [2][groups][RS_BINS] the same counts per group of tiles: the pass in flight / the next one
-  int rs_groups = 0;
-  unsigned rs_seq = 0;
+  // ---- what a re-sort leaves for the substep: written by resort.hip (do_import, rebin), read by everyone.  What only the re-sort
+  // itself touches -- sort buffers, block flags, tables and their capacities, face sort, original-index adjacency -- is ResortState
+  ResortState *rs = nullptr;
+  Bufs buf[2]{};  // the particles in sorted order; the re-sort gathers from buf[cur] into the other and flips cur
+  int cur = 0;
+  int *perm[2] = {nullptr, nullptr}, *inv = nullptr;   // sorted slot -> caller's index (of buf[i]) and back
+  SortKey *keys[2] = {nullptr, nullptr};               // keys[1]: the sorted keys
+  int *face_slot = nullptr, *adj_s = nullptr;          // cloth topology in sorted slots: [3][n_e] corners, [adj_K][n_v] (element, corner) of a vertex
+  int adj_K = 0;
+  int *alist = nullptr, *ab_flag = nullptr;            // active blocks: the list and [nblocks] flags
+  int n_P = 0, n_A = 0;                                // particle blocks, active blocks
+  ChunkRec *chunks = nullptr, *chunks_g = nullptr;     // p2g list, g2p list (= p2g list unless there are ghost copies)
+  int n_chunks = 0, n_chunks_g = 0;
+  FaceBin *fbins = nullptr;                            // body-face bins (collider gather) on the active list
+  int *fidx = nullptr;                                 // [n_f][3] face vertex ids in bin order
+  int n_fbins = 0;
+  bool face_flag_seen = false;    // some ring entry since the last face sort had the face bit set (poll_drift_flags; the face sort clears it)
+  // the mass span of the import, read back by the next re-sort: decides the chunk tile of p2g (read_mass_span, resort.hip)
+  bool mass_span_pending = false, p2g_fixed_now = true;
+  float mass_span = 1.0f;
+  bool all_simulated = false;     // no particle with selection != 0 (counted at every import with the mass span)
+  // ---- (end of the re-sort's block)
   bool sort_rocprim = false;   // MPMHIP_SORT=rocprim: the library's sort instead (same permutation)
   GridPtrs g{};
-  int *pb_flag = nullptr, *pb_index = nullptr, *ab_flag = nullptr, *ab_index = nullptr;
-  int *fc_gsum = nullptr, *fc_tcount = nullptr;  // [2][fc_groups], [2][fc_tiles]: flagged blocks per group / tile (k_flag_count)
-  int fc_tiles = 0, fc_groups = 0, n_clear = 0;  // n_clear: ints from pb_flag on that a re-sort starts from zeroed
-  int *plist = nullptr, *alist = nullptr, *ranges = nullptr;
-  ChunkRec *chunks = nullptr, *chunks_g = nullptr;  // p2g list, g2p list (= p2g list unless there are ghost copies)
-  int n_chunks_g = 0;
   bool ghost_g2p = false;  // multi-GPU: ghost copies (selection == 2) gather for themselves
-  int cap_P = 0, cap_A = 0, cap_chunks = 0, cap_R = 0;  // cap_P: capacity the block tables are built with (grows on demand)
-  int alloc_P = 0;     // allocated entries of plist
-  int *rcnt = nullptr; // device: counts of the last re-sort (RC_*)
   int64_t stat_steps = 0;
-  int n_P = 0, n_A = 0, n_chunks = 0;
   int *h_pin = nullptr;  // pinned host scratch, PIN_N ints (PIN_*)
-  // host staging of the re-sort in pinned memory: device->host copies really are asynchronous, and the chunk table can
-  // be uploaded without waiting for the copy (the next re-sort synchronises long before it touches the buffer again)
-  template <class T>
-  struct Pinned {
-    T *p = nullptr;
-    size_t n = 0, cap = 0;
-    bool reserve(size_t want) {
-      if (want <= cap) return true;
-      size_t nc = want + want / 2 + 256;
-      T *q = nullptr;
-      if (hipHostMalloc((void **)&q, nc * sizeof(T), hipHostMallocDefault) != hipSuccess) return false;
-      if (p) { memcpy(q, p, n * sizeof(T)); (void)hipHostFree(p); }
-      p = q; cap = nc;
-      return true;
-    }
-    bool resize(size_t want) { if (!reserve(want)) return false; n = want; return true; }
-    bool push_back(const T &v) { if (n == cap && !reserve(n + 1)) return false; p[n++] = v; return true; }
-    void clear() { n = 0; }
-    size_t size() const { return n; }
-    T *data() { return p; }
-    T &operator[](size_t i) { return p[i]; }
-    T *begin() { return p; }
-    T *end() { return p + n; }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; n = cap = 0; }
-  };
-  Pinned<int> h_ranges, h_plist;
-  Pinned<ChunkRec> h_chunks, h_chunks_g;
   bool elem_pending = false;  // element finalise of the last substep still to be done (fused into the next stress)
-  bool all_simulated = false;      // no particle with selection != 0 (counted at every import with the mass span)
   int steps_since_rebin = 0;
   volatile int *h_sig = nullptr;  // pinned, host-mapped, written by the kernels (GridPtrs::host_sig)
   unsigned sig_seq = 0;           // step_id of the last p2g launch issued (wraps)
   unsigned sig_at_rebin = 0;      // sig_seq when the last re-sort finished: ring entries up to it speak about the old order
-  bool face_flag_seen = false;    // some ring entry since the last face sort had the face bit set
   int host_lead = 6;              // substeps the host may run ahead of the GPU (MPMHIP_HOST_LEAD)
   bool have_order = false;
   int64_t rebins = 0;
@@ -324,7 +284,6 @@ struct FastState {
   std::vector<void *> allocs;
 };
 
-
 template <class T>
 int dalloc(mpmhip_ctx *c, T **p, size_t count, bool zero = true) {
   size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
@@ -348,14 +307,15 @@ inline void kstamp_launch(mpmhip_ctx *c, K kernel, unsigned grid, unsigned block
   }
 }
 
-
 // ---- functions shared by the translation units of the fast back end ------------------------------------------------------
 // resort.hip
 int alloc_bufs(mpmhip_ctx *c, Bufs &b);
-int ensure_cap(mpmhip_ctx *c, int **p, int *cap, int need, int per);
-int scan_flags(mpmhip_ctx *c, const int *flag, int *index, int n, int *total);
+int resort_alloc(mpmhip_ctx *c);                  // ResortState and the buffers of FastState's re-sort block (fast_init)
+int resort_alloc_face_sort(mpmhip_ctx *c, int nf);  // ... the arrays of the body-face sort (first mesh collider)
+void resort_free(FastState *f);                     // (device memory goes with FastState::allocs)
 int do_import(mpmhip_ctx *c);
 int rebin(mpmhip_ctx *c);
+int compact_shared_blocks(mpmhip_ctx *c, const int *flag, int n, int *index, int *list, int cap, int *total);
 // fast.hip
 int flush_elements(mpmhip_ctx *c);
 int flush_g2p(mpmhip_ctx *c);  // launches the deferred g2p of a G2P2G sequence
@@ -371,6 +331,5 @@ void launch_stress_trad(mpmhip_ctx *c, float dt);
 void launch_g2p(mpmhip_ctx *c, bool fused, bool two, float dt, const GridParams &gp, const BCList &bcl);
 void launch_g2p2g(mpmhip_ctx *c, unsigned grid, float dt, const GridRead &rd, const SplatArgs &sa, const TradParams &tp, const GridParams &gp,
                   const BCList &bcl);
-
 
 }  // namespace mpm
