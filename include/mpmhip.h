@@ -470,6 +470,25 @@ int mpmhip_densify_emit(int32_t device, void *stream, int32_t n, int32_t n_faces
 /* reset_opacity (:284-287): out[i] = log(x / (1 - x)), x = min(sigmoid(opacity[i]), 0.01). */
 int mpmhip_reset_opacity(int32_t device, void *stream, int64_t n, const float *opacity, float *out);
 
+/* ---- the optimiser step of the appearance loop --------------------------------------------
+ * gaussians.optimizer.step() (train_appearance.py:260-261) for the torch.optim.Adam(l, lr=0.0, eps=1e-15) that
+ * scene/gaussian_model.py:207-234 and scene/mesh_gaussian_model.py:148-170 set up: no amsgrad, no weight decay.  One call updates
+ * n_tensors fp32 tensors in place, in one launch per MPMHIP_ADAM_MAX_TENSORS of them (the table of a launch is its kernel
+ * argument); a tensor is worked on in chunks of MPMHIP_ADAM_CHUNK elements.  Every array is a HOST array of length n_tensors; the
+ * pointers in params / grads / exp_avg / exp_avg_sq are device pointers to counts[i] floats.  Per element
+ *   m' = m + w1 (g - m),   v' = v beta2 + w2 g g,   p' = p - step_size (m' / (sqrt(v') / bc2_sqrt + eps))
+ * in fp32 without contraction and in this order, with the caller's scalars: w1 = 1 - beta1, w2 = 1 - beta2, bc2_sqrt =
+ * sqrt(1 - beta2^step), step_size = lr / (1 - beta1^step), computed in double and rounded once.  update_param[i] == 0 (a group
+ * with lr == 0): params[i] is neither read nor written, the moments still move.  Nothing is allocated, copied or synchronised.
+ * MPMHIP_ERR_INVALID: a negative n_tensors or count, a NULL array with n_tensors > 0, a NULL tensor pointer with a positive
+ * count, a count above what a launch can index (2^31 / MPMHIP_ADAM_MAX_TENSORS chunks).  Tensors without elements are skipped. */
+#define MPMHIP_ADAM_CHUNK 4096
+#define MPMHIP_ADAM_MAX_TENSORS 48
+int mpmhip_adam_step(int32_t device, void *stream, int32_t n_tensors, void *const *params, const void *const *grads,
+                     void *const *exp_avg, void *const *exp_avg_sq, const int64_t *counts, const float *step_size,
+                     const float *bc2_sqrt, const float *w1, const float *beta2, const float *w2, const float *eps,
+                     const uint8_t *update_param);
+
 /* MPMWARP.export_particle_cov_to_torch (warp_mpm/mpm_solver.py:543-561) = kernel compute_cov_from_F
  * (warp_mpm/mpm_utils.py:1108-1132): new_cov[6p..] = upper triangle (xx xy xz yy yz zz) of F_trial[p] * sym(particle_cov[6p..])
  * * F_trial[p]^T for p < n (= n_particles - n_vertices).  Stand-alone map on [dev] arrays in the reference's AoS layout. */

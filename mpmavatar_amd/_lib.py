@@ -116,6 +116,7 @@ SIGNATURES = {
     "mpmhip_densify_plan": (C.c_int, [C.c_int32, vp, C.c_int32, C.c_int32] + [vp] * 6 + [C.c_float] * 4 + [C.c_int32, vp, C.c_int64, vp]),
     "mpmhip_densify_emit": (C.c_int, [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 7 + [C.c_int64, C.c_int32] + [vp] * 8),
     "mpmhip_reset_opacity": (C.c_int, [C.c_int32, vp, C.c_int64, vp, vp]),
+    "mpmhip_adam_step": (C.c_int, [C.c_int32, vp, C.c_int32] + [vp] * 12),
     "mpmhip_face_areas":(C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, vp]),
     "mpmhip_mesh_sample": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp]),
     "mpmhip_nn_dist2": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp]),
