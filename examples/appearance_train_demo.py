@@ -12,13 +12,18 @@ the optimiser (train_appearance.py:112 and :260-261) and across a densification 
     once each: reset_opacity(_opacity, optimizer)             -> mpmhip_reset_opacity, in front of the first iteration
                densify_and_prune(...) + swap_into(optimizer)  -> mpmhip_densify_plan / _emit, half way
 
-    python examples/appearance_train_demo.py [--steps 30] [--size 64]
+    python examples/appearance_train_demo.py [--steps 30] [--size 64] [--shadow-net]
 
 The scene is the one of appearance_step_demo.py with colours (a 320-face icosphere, two Gaussians per face, degree-1 SH, an 8 x 8
 shadow map standing in for the output of the shadow network); ``cams`` is the affine of the rendered image (train_appearance.py:126),
 three gains and three offsets.  The rates are this toy scene's, not the reference's defaults, and so are the densification
 thresholds (examples/densify_demo.py says why).  The opacities are reset before the first iteration, so every loss printed is part
 of the recovery from it; the demo fails if the last loss is not below the first.
+
+``--shadow-net`` puts the first line of the colour path (train_appearance.py:120) in place of the bare map: per step
+``AOBaker.bake(verts)`` -> ``ShadowUNet(ao_map)["shadow_map"]`` -> ``shaded_colors``, with ``shadow_net.parameters()`` as the
+``shadow`` group.  The sphere's UVs are its vertex directions (front and back share texels; the baker keeps one face per texel),
+the AO map is 32 x 32, the network works at 16 x 16 with four channels and hands the 8 x 8 map on.
 """
 import argparse
 import os
@@ -30,14 +35,17 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from appearance_step_demo import SH_DEGREE, Scene  # noqa: E402
+from appearance_step_demo import MAP_SIZE, SH_DEGREE, Scene  # noqa: E402
+from mpmavatar_amd.ao_bake import AOBaker  # noqa: E402
 from mpmavatar_amd.densify import DensifyStats, adam_moments, densify_and_prune, reset_opacity  # noqa: E402
 from mpmavatar_amd.image_loss import image_loss  # noqa: E402
 from mpmavatar_amd.optim import FusedAdam, appearance_param_groups, update_learning_rate  # noqa: E402
 from mpmavatar_amd.rasterizer import GaussianRasterizer  # noqa: E402
 from mpmavatar_amd.render_inputs import BoundGaussians  # noqa: E402
+from mpmavatar_amd.shadow_net import ShadowUNet  # noqa: E402
 
 EXTENT = 1.0
+AO_SIZE = 32
 # the names of arguments/__init__.py:115-126 with rates for this scene
 OPT = SimpleNamespace(position_lr_init=5e-3, position_lr_final=5e-4, position_lr_delay_mult=0.01, position_lr_max_steps=30,
                       verts_lr_init=1e-3, verts_lr_final=1e-4, verts_lr_delay_mult=0.01, verts_lr_max_steps=30, feature_lr=1e-2,
@@ -48,13 +56,24 @@ class TrainScene(Scene):
     """the scene of appearance_step_demo.py --colors whose render keeps ``means2D`` as a leaf and whose image passes the camera's
     affine"""
 
-    def __init__(self, size):
+    def __init__(self, size, shadow_net=False):
         super().__init__(size, colors=True)
         dev = self.verts_orig.device
         self.cam_m, self.cam_c = torch.nn.Parameter(torch.ones(3, device=dev)), torch.nn.Parameter(torch.zeros(3, device=dev))
+        self.baker = self.shadow_net = None
+        if shadow_net:
+            direction = self.verts_orig / self.verts_orig.norm(dim=1, keepdim=True)
+            vt = (0.5 + 0.5 * direction[:, :2]).cpu().numpy().astype(np.float32)
+            self.baker = AOBaker(self.frames.faces, vt, self.frames.faces.cpu().numpy().astype(np.int32), height=AO_SIZE, width=AO_SIZE,
+                                 samples=64)
+            with torch.no_grad():
+                ao_mean = self.baker.bake(self.verts_orig)[None].cpu()
+            self.shadow_net = ShadowUNet(uv_size=MAP_SIZE, ao_mean=ao_mean, shadow_size=16, n_dims=4, biases=False).to(dev)
 
     def render(self):
         self.frames.set_mesh_by_verts(self.verts_orig + self.verts_offset)
+        if getattr(self, "shadow_net", None) is not None:       # train_appearance.py:120: this frame's AO map through the network
+            self.shadow_map = self.shadow_net(self.baker.bake((self.verts_orig + self.verts_offset).detach())[None])["shadow_map"]
         args = self.gaussians.render_inputs(self.frames, override_color=self.colors)
         args["colors_precomp"] = self.gaussians.shaded_colors(args["means3D"], self.campos, SH_DEGREE, shadow_map=self.shadow_map, sampler=self.sampler)
         self.means2D = args["means2D"].requires_grad_(torch.is_grad_enabled())
@@ -71,11 +90,13 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--size", type=int, default=64)
+    ap.add_argument("--shadow-net", action="store_true", help="train a ShadowUNet behind AOBaker in place of the bare shadow map")
     a = ap.parse_args(argv)
-    sc = TrainScene(a.size)
+    sc = TrainScene(a.size, a.shadow_net)
     p = sc.params
+    shadow = list(sc.shadow_net.parameters()) if a.shadow_net else [p["shadow_map"]]
     groups = appearance_param_groups(p["_xyz"], p["_features_dc"], p["_features_rest"], p["_opacity"], p["_scaling"], p["_rotation"],
-                                     p["verts_offset"], [sc.cam_m, sc.cam_c], [p["shadow_map"]], OPT, spatial_lr_scale=1.0)
+                                     p["verts_offset"], [sc.cam_m, sc.cam_c], shadow, OPT, spatial_lr_scale=1.0)
     opt = FusedAdam(groups, lr=0.0, eps=1e-15)
     p["_opacity"] = reset_opacity(p["_opacity"], opt)
     print(f"reset_opacity: every opacity at most {float(torch.sigmoid(p['_opacity'].detach()).max()):.3f}")

@@ -376,6 +376,55 @@ int mpmhip_shade_colors_backward(int32_t device, void *stream, int32_t n, int32_
                                  const int32_t *face_start, const int32_t *face_items, const int32_t *texel_start,
                                  const int32_t *texel_items, float *d_shadow_map, float *scratch);
 
+/* ---- the shadow network in front of the colours (scene/shadow.py:14-181, called at train_appearance.py:120 and :201) --------------
+ * ShadowUNet over scene/network.py (Conv2dUB :277-329, weight_norm_wrapper :158-266, Conv2dWN / Conv2dWNUB :471-473), for
+ * interp_mode = "bilinear" and a constant ao_mean, forward and backward.  With S = shadow_size, U = uv_size,
+ * C = n_dims (4 or 8) and level sizes s_i = S >> i:
+ *   x = nearest(ao_map [n, in_h, in_w] -> S x S) - ao_mean [S*S]               (F.interpolate(size=), legacy nearest; shadow.py:138-141)
+ *   layers 0..3 (encoder i, at s_i): lrelu(conv3x3 + untied bias), the input of i > 0 read bilinearly (align_corners) from s_{i-1}
+ *   layers 4..7 (decoder j, at s_{3-j}): the same over [up(decoder j-1), encoder 3-j] (j = 0: encoder 3 alone)
+ *   layer 8 (shadow_pred, C -> 1): lowres = sigmoid(conv3x3 + bias + beta); the bias is [1] (Conv2dWN, biases = False) or [S*S]
+ *   shadow_map [n, U, U] = bilinear(lowres, align_corners = False); with U == S a bit-exact copy
+ * Weights of layer L: weight_v [cout, cin, 3, 3], weight_g [cout], w[o] = v[o] g[o] / ||v||_F with one norm over the whole of v;
+ * bias [cout, s, s].  Channels (cin, cout): (1, C), three times (C, C), (C, C), three times (2C, C), (C, 1).
+ * Every discrete decision and weight of a resampling is read from `tables`, a DEVICE copy of the blob that
+ * mpmhip_shadow_workspace_bytes fills on the host for (in_h, in_w, shadow_size, uv_size); forward and backward share it, the
+ * adjoint of a resampling is a gather over its inverse lists, and nothing uses a floating-point atomic: the same input gives the same
+ * bits.  d_weight_v / d_weight_g / d_bias are read by mpmhip_shadow_backward alone: written in full where given, NULL = not wanted. */
+#define MPMHIP_SHADOW_LAYERS 9
+typedef struct {
+  int32_t n, in_h, in_w, shadow_size, uv_size, n_dims;
+  int32_t untied_head_bias; /* 0: the head's bias is [1] (biases = False); 1: [shadow_size^2] */
+  int32_t reserved_;
+  float lrelu_slope, beta;
+  const float *ao_mean;
+  const void *tables;
+  const float *weight_v[MPMHIP_SHADOW_LAYERS];
+  const float *weight_g[MPMHIP_SHADOW_LAYERS];
+  const float *bias[MPMHIP_SHADOW_LAYERS];
+  float *d_weight_v[MPMHIP_SHADOW_LAYERS];
+  float *d_weight_g[MPMHIP_SHADOW_LAYERS];
+  float *d_bias[MPMHIP_SHADOW_LAYERS];
+} mpmhip_shadow_desc;
+/* The sizes for desc's n, in_h, in_w, shadow_size, uv_size and n_dims (its pointers are not read): the workspace both passes take
+ * and the table blob; host_tables != NULL: table_bytes bytes of HOST memory are filled with the blob, for the caller to copy to the
+ * device once.  Host arithmetic: the outputs are written whenever the arguments are valid, and the return is then that of the
+ * device check.  MPMHIP_ERR_INVALID: n < 0 or > 65535, a size < 1 or > 8192, shadow_size < 8, n_dims not 4 or 8, a NULL output. */
+int mpmhip_shadow_workspace_bytes(int32_t device, void *stream, const mpmhip_shadow_desc *desc, int64_t *out_workspace_bytes,
+                                  int64_t *out_table_bytes, void *host_tables);
+/* shadow.py:135-181.  ao_map [n*in_h*in_w]; out_lowres [n*S*S], out_shadow_map [n*U*U]; out_ao_map [n*S*S], the resized input the
+ * reference returns beside them, or NULL.  The workspace keeps the normalised weights and the eight activations for the backward
+ * pass; a caller that wants no gradient may reuse it at once.  10 launches, 11 where U != S.  MPMHIP_ERR_INVALID also: a negative
+ * or non-finite lrelu_slope, a NULL input, parameter or output, a workspace that is too small.  n == 0: MPMHIP_OK, no launch. */
+int mpmhip_shadow_forward(int32_t device, void *stream, const mpmhip_shadow_desc *desc, const float *ao_map, void *workspace,
+                          int64_t workspace_bytes, float *out_ao_map, float *out_lowres, float *out_shadow_map);
+/* The gradients of every parameter desc names, from g_shadow_map [n*U*U] and g_lowres [n*S*S] (either may be NULL = zero), over the
+ * workspace mpmhip_shadow_forward left and the lowres it wrote.  The derivative of LeakyReLU at exactly 0 is the slope, as in torch;
+ * an untied bias gradient is the pre-activation gradient itself, summed over n.  12 launches.  ao_map and ao_mean are constants, as
+ * in the reference.  Nothing wanted: MPMHIP_OK, no launch. */
+int mpmhip_shadow_backward(int32_t device, void *stream, const mpmhip_shadow_desc *desc, const float *ao_map, const float *lowres,
+                           const float *g_shadow_map, const float *g_lowres, void *workspace, int64_t workspace_bytes);
+
 /* ---- the regularisation terms of the appearance loop (train_appearance.py:136-150) ------------------------------------------------
  * What the reference computes between render(...) and loss.backward() besides the image loss, as two fused ops with exact backward
  * passes.  Stand-alone maps on [dev] arrays; nothing allocates or synchronises; fp32 data, sums in fp64 in a fixed order, no

@@ -73,6 +73,13 @@ class RasterStats(C.Structure):
     _fields_ = [("n_entries", C.c_int64), ("max_tile_entries", C.c_int32), ("n_visible", C.c_int32), ("scratch_bytes", C.c_int64)]
 
 
+class ShadowDesc(C.Structure):
+    _fields_ = [("n", C.c_int32), ("in_h", C.c_int32), ("in_w", C.c_int32), ("shadow_size", C.c_int32), ("uv_size", C.c_int32),
+                ("n_dims", C.c_int32), ("untied_head_bias", C.c_int32), ("reserved_", C.c_int32), ("lrelu_slope", C.c_float),
+                ("beta", C.c_float), ("ao_mean", vp), ("tables", vp), ("weight_v", vp * 9), ("weight_g", vp * 9), ("bias", vp * 9),
+                ("d_weight_v", vp * 9), ("d_weight_g", vp * 9), ("d_bias", vp * 9)]
+
+
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
 SIGNATURES = {
     "mpmhip_version": (C.c_int, []),
@@ -107,6 +114,9 @@ SIGNATURES = {
     "mpmhip_face_frames_backward": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, C.c_int32] + [vp] * 10),
     "mpmhip_shade_colors": (C.c_int, [C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp]),
     "mpmhip_shade_colors_backward": (C.c_int, [C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32] + [vp] * 11),
+    "mpmhip_shadow_workspace_bytes": (C.c_int, [C.c_int32, vp, C.POINTER(ShadowDesc), C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
+    "mpmhip_shadow_forward": (C.c_int, [C.c_int32, vp, C.POINTER(ShadowDesc), vp, vp, C.c_int64, vp, vp, vp]),
+    "mpmhip_shadow_backward": (C.c_int, [C.c_int32, vp, C.POINTER(ShadowDesc), vp, vp, vp, vp, vp, C.c_int64]),
     "mpmhip_mesh_reg_forward": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32] + [vp] * 7),
     "mpmhip_mesh_reg_backward": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32] + [vp] * 9),
     "mpmhip_gauss_reg_forward": (C.c_int, [C.c_int32, vp, C.c_int32] + [vp] * 5 + [C.c_float, C.c_float] + [vp] * 3),
