@@ -33,6 +33,10 @@ bool fast_mode(const mpmhip_ctx *c) { return c->cfg.mode == MPMHIP_MODE_FAST; }
 int dist_only(mpmhip_ctx *c, bool also = true) {
   return (fast_mode(c) && also) ? MPMHIP_OK : fail(c, MPMHIP_ERR_INVALID, "dist: only the fast mode shards across GPUs");
 }
+// ... and so do the debugging ones, which also need its live state
+int fast_only(mpmhip_ctx *c, const char *who) {
+  return (fast_mode(c) && c->fast) ? MPMHIP_OK : fail(c, MPMHIP_ERR_INVALID, std::string(who) + ": fast mode only");
+}
 
 // Preconditions of every stepping entry point.  The back ends read the body mesh through cur_pts + cur_f * cur_vel
 // (device-to-device; the reference's .cpu().numpy() round trip per substep, mpm_solver.py:282-302, is not reproduced).
@@ -40,9 +44,7 @@ int step_prepare(mpmhip_ctx *c, const float *mesh_x, const float *mesh_v, float 
   if (!c->st_bound || !c->md_bound) return fail(c, MPMHIP_ERR_STATE, "step: state/model not bound");
   if (n_joint_t < 0 || n_joint_t > c->n_trad) return fail(c, MPMHIP_ERR_INVALID, "step: n_joint_t out of range");
   if ((mesh_x || mesh_v) && !c->mesh_points) return fail(c, MPMHIP_ERR_STATE, "step: mesh_x/mesh_v given but no body mesh");
-  c->cur_pts = mesh_x ? mesh_x : c->mesh_points;
-  c->cur_vel = mesh_v ? mesh_v : c->mesh_vel;
-  c->cur_f = (mesh_x && mesh_v) ? mesh_f : 0.0f;
+  set_body_view(c, mesh_x, mesh_v, mesh_f);
   return MPMHIP_OK;
 }
 
@@ -378,8 +380,7 @@ static int step_checked(mpmhip_ctx *c, const StepArgs &a) {
     ScopedPhase ph(c, "update_mesh_positions");
     mesh_store(c, a.mesh_x, a.mesh_v);
   }
-  c->time = c->time + c->time_inc(a.dt);  // mpm_solver.py:536
-  c->substeps += 1;
+  advance_time(c, a.dt);
   return MPMHIP_OK;
 }
 
@@ -397,7 +398,7 @@ int mpmhip_steps(mpmhip_ctx *c, float dt, int32_t n, const float *mesh_x, const 
   if (n < 0) return fail(c, MPMHIP_ERR_INVALID, "steps: n < 0");
   const bool fast = fast_mode(c) && c->fast && c->st_bound && c->md_bound && (!(mesh_x || mesh_v) || c->mesh_points);
   if (fast) {   // a body that does not move during this call is splatted once, not n times (fast_body_at_rest_begin, fast.hip)
-    c->cur_vel = mesh_v ? mesh_v : c->mesh_vel;
+    set_body_view(c, mesh_x, mesh_v, 0.0f);  // (its velocities are what is looked at; every substep sets its own view)
     int rc = fast_body_at_rest_begin(c, n);
     if (rc) return rc;
   }
@@ -480,8 +481,7 @@ int mpmhip_dist_step_end(mpmhip_ctx *c) {
   StepArgs a{};
   int rc = fast_dist_phase(c, 2, a);
   if (rc) return rc;
-  c->time = c->time + c->time_inc(c->fast_dt);
-  c->substeps += 1;
+  advance_time(c, c->fast_dt);
   return MPMHIP_OK;
 }
 
@@ -547,7 +547,7 @@ int mpmhip_export_grid(mpmhip_ctx *c, float *grid_m, float *grid_v_in, float *gr
 
 int mpmhip_set_debug_flags(mpmhip_ctx *c, int32_t flags) {
   CHECK_CTX(c);
-  if (!fast_mode(c) || !c->fast) return fail(c, MPMHIP_ERR_INVALID, "set_debug_flags: fast mode only");
+  if (int rc = fast_only(c, "set_debug_flags")) return rc;
   return fast_set_debug_flags(c, flags);
 }
 
@@ -567,26 +567,26 @@ int mpmhip_dist_halo_transport(mpmhip_ctx *c, int32_t *out) {
 
 int mpmhip_dist_fused_halo_steps(mpmhip_ctx *c, int64_t *out) {
   if (!c || !out) return MPMHIP_ERR_INVALID;
-  if (!fast_mode(c) || !c->fast) return fail(c, MPMHIP_ERR_INVALID, "dist_fused_halo_steps: fast mode only");
+  if (int rc = fast_only(c, "dist_fused_halo_steps")) return rc;
   *out = fast_dist_fused_halo_steps(c);
   return MPMHIP_OK;
 }
 
 int mpmhip_debug_counter(mpmhip_ctx *c, int32_t index, int64_t *out) {
   CHECK_CTX(c);
-  if (!fast_mode(c) || !c->fast) return fail(c, MPMHIP_ERR_INVALID, "debug_counter: fast mode only");
+  if (int rc = fast_only(c, "debug_counter")) return rc;
   return fast_debug_counter(c, index, out);
 }
 
 int mpmhip_debug_wgtrace(mpmhip_ctx *c, int32_t kernel, uint64_t *out, int32_t max_wg) {
   if (!c) return MPMHIP_ERR_INVALID;
-  if (!fast_mode(c) || !c->fast) return fail(c, MPMHIP_ERR_INVALID, "debug_wgtrace: fast mode only");
+  if (int rc = fast_only(c, "debug_wgtrace")) return rc;
   return fast_debug_wgtrace(c, kernel, out, max_wg);
 }
 
 int mpmhip_debug_sort(mpmhip_ctx *c, const uint32_t *keys_in, int32_t n, int32_t bits, uint32_t *keys_out, int32_t *order_out) {
   CHECK_CTX(c);
-  if (!fast_mode(c) || !c->fast) return fail(c, MPMHIP_ERR_INVALID, "debug_sort: fast mode only");
+  if (int rc = fast_only(c, "debug_sort")) return rc;
   if (n < 0 || bits < 1 || bits > 32 || (n > 0 && (!keys_in || !keys_out || !order_out)))
     return fail(c, MPMHIP_ERR_INVALID, "debug_sort: bad arguments");
   return fast_debug_sort(c, keys_in, n, bits, keys_out, order_out);

@@ -61,7 +61,8 @@ struct Phase {
   int64_t kernel_samples = 0;
 };
 
-struct FastState;  // defined in fast.hip
+struct FastState;  // fast_state.hpp; the multi-GPU part of it is DistState, defined in dist.hip
+struct DistState;
 
 }  // namespace mpm
 
@@ -135,6 +136,16 @@ inline int fail(mpmhip_ctx *ctx, int code, const std::string &msg) {
   } while (0)
 
 inline size_t G3(const mpmhip_ctx *c) { return (size_t)c->cfg.n_grid * c->cfg.n_grid * c->cfg.n_grid; }
+
+// The body mesh as the coming substep sees it, cur_pts + cur_f * cur_vel: the caller's arrays where given, the context's own copy
+// otherwise; the advection factor holds only where both are the caller's.
+inline void set_body_view(mpmhip_ctx *c, const float *mesh_x, const float *mesh_v, float mesh_f) {
+  c->cur_pts = mesh_x ? mesh_x : c->mesh_points;
+  c->cur_vel = mesh_v ? mesh_v : c->mesh_vel;
+  c->cur_f = (mesh_x && mesh_v) ? mesh_f : 0.0f;
+}
+// a substep is done: MPMWARP.time, mpm_solver.py:536
+inline void advance_time(mpmhip_ctx *c, float dt) { c->time = c->time + c->time_inc(dt); c->substeps += 1; }
 
 // profiling brackets: no-ops unless enabled (then one sync per phase, like ScopedTimer(synchronize=True))
 struct ScopedPhase {

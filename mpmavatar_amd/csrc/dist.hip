@@ -1,8 +1,90 @@
 // dist.hip -- multi-GPU: halo / ghost kernels, peer links (HIP IPC), the RCCL binding and the in-library sharded loop.
-// (split out of fast.hip in round 4; shared device code: fast_device.hpp, shared host state: fast_state.hpp)
+// (shared device code: fast_device.hpp; the per-peer tables the kernels take and their builders: halo_tables.hpp)
+// The state of all this is DistState, below: defined here, allocated and freed here (dist_alloc / dist_free), and FastState holds a
+// pointer to it that no other translation unit looks behind.  fast.hip asks three things of it, by name (fast_state.hpp): alloc / free,
+// "is the fused halo in force for this substep?", and "what of the halo rides in this p2g launch?".
 #include "fast_state.hpp"
 
 namespace mpm {
+
+struct Rccl {  // entry points resolved with dlsym: libmpmhip.so itself does not link librccl
+  void *h = nullptr;
+  ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;
+  ncclResult_t (*CommInitRank)(ncclComm_t *, int, ncclUniqueId, int) = nullptr;
+  ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
+  ncclResult_t (*GroupStart)() = nullptr;
+  ncclResult_t (*GroupEnd)() = nullptr;
+  ncclResult_t (*Send)(const void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
+  ncclResult_t (*Recv)(void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
+  ncclResult_t (*AllGather)(const void *, void *, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
+  ncclResult_t (*AllReduce)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
+  const char *(*GetErrorString)(ncclResult_t) = nullptr;
+  ncclComm_t comm = nullptr;
+  int rank = 0, world = 1;
+  bool load(std::string &err) {
+    if (h) return true;
+    // MPMHIP_RCCL_LIB: another library with the same ten entry points (tests/mock_rccl: shared-memory stand-in that lets
+    // 2-3 ranks share the one GPU of a test box, which RCCL itself refuses)
+    const char *over = getenv("MPMHIP_RCCL_LIB");
+    if (over && *over) {
+      h = dlopen(over, RTLD_NOW | RTLD_LOCAL);
+      if (!h) { err = std::string("dlopen MPMHIP_RCCL_LIB=") + over + ": " + dlerror(); return false; }
+      // never silently: the collective library of a production run must be RCCL
+      fprintf(stderr, "[mpmhip] WARNING: MPMHIP_RCCL_LIB is set -- the multi-GPU exchange uses %s INSTEAD OF librccl.so (test hook)\n", over);
+    }
+    if (!h) h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
+    if (!h) h = dlopen("/opt/rocm/lib/librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
+    if (!h) { err = std::string("dlopen librccl.so.1: ") + dlerror(); return false; }
+    auto sym = [&](const char *n) { void *p = dlsym(h, n); if (!p) err = std::string("dlsym ") + n; return p; };
+    *(void **)&GetUniqueId = sym("ncclGetUniqueId"); *(void **)&CommInitRank = sym("ncclCommInitRank");
+    *(void **)&CommDestroy = sym("ncclCommDestroy"); *(void **)&GroupStart = sym("ncclGroupStart");
+    *(void **)&GroupEnd = sym("ncclGroupEnd"); *(void **)&Send = sym("ncclSend"); *(void **)&Recv = sym("ncclRecv");
+    *(void **)&AllGather = sym("ncclAllGather"); *(void **)&GetErrorString = sym("ncclGetErrorString");
+    *(void **)&AllReduce = sym("ncclAllReduce");
+    return GetUniqueId && CommInitRank && CommDestroy && GroupStart && GroupEnd && Send && Recv && AllGather && AllReduce &&
+           GetErrorString;
+  }
+};
+
+// One neighbour rank: the record the launches and the exchange read (DistPeer: shared blocks, halo and ghost buffers, the link) plus
+// what only the in-library loop keeps of it, all buffers owned here.  A peer that came through the ABI (mpmhip_dist_set_peers: the
+// Python-driven transport) is the DistPeer part alone: no rank, no link, nothing owned.
+struct RcclPeer : DistPeer {
+  RcclPeer() = default;
+  explicit RcclPeer(const mpmhip_dist_peer &p) : DistPeer(p) {}
+  int rank = -1;
+  int *flag = nullptr, *index = nullptr;  // [nblocks] shared with this rank / position in blocks[] (per collective re-sort)
+  int cap_blocks = 0;                     // capacity of blocks[], halo_send, halo_recv
+  unsigned char *hbuf = nullptr;          // device staging of the two IPC handles (mine at 0, theirs at 128)
+  // (the ABI's record points at its lists as const; the loop's own blocks[] is an allocation of this file, which the re-sort fills)
+  int *own_blocks() const { return const_cast<int *>(blocks); }
+};
+
+struct DistState {
+  Rccl rccl;
+  // THE peer list, of either transport: filled by mpmhip_rccl_set_ghosts + every collective re-sort (in-library loop) or replaced by
+  // mpmhip_dist_set_peers (Python-driven).  The tables are built from it and the exchange walks it: one list, nothing to keep paired.
+  std::vector<RcclPeer> peers;
+  unsigned char *map_all = nullptr;  // [world][nblocks] active-block byte maps
+  StepArgs dist_args{};              // the substep in flight (phase 0 stores them for phases 1 and 2)
+  bool link_want = true, link_decided = false, link_on = false;  // peer-mapped halos: asked for / decided collectively / in use
+  // fused halo (peer-mapped halos only): pack workgroups ride in the p2g launch, g2p adds the neighbour's share while it
+  // stages its tile (PackArgs, HaloIn) -- no pack / add kernels in the substep.  Decided per collective re-sort (local decision:
+  // what goes over the links is the same either way).  MPMHIP_DIST_FUSED_HALO=0: keep the two kernels.
+  bool fused_want = true, fused_halo = false;
+  int *halo_slot = nullptr, *halo_multi = nullptr;
+  unsigned *pack_done = nullptr, pack_target = 0;
+  int64_t fused_halo_steps = 0;  // substeps that ran without pack / add kernels (mpmhip_dist_fused_halo_steps)
+  unsigned halo_seq = 0;         // substeps exchanged so far (+ handshake rounds): flag value and buffer parity (wraps: the
+                                 // kernels compare (int)(flag - seq), long trainings run billions of substeps)
+  bool dist_keep_cur = false;    // re-sort inside mpmhip_rccl_steps: the caller's mesh pointers are valid
+  // adaptive collective re-sorts (mpmhip_rccl_steps with rebin_interval <= 0): the ranks' drift flags are max-reduced
+  // every DIST_POLL substeps and read DIST_LAG substeps later, so every rank takes the same decision at the same substep
+  int dist_since = 0;
+  bool dist_resort = false, dflag_in_flight = false, rccl_sorted = false;
+  int64_t dflag_check_at = 0;
+  unsigned dflag_seq = 0;  // sequence number of the last reduction posted to host memory (k_post_flag; wraps)
+};
 
 namespace {
 
@@ -104,6 +186,46 @@ __global__ void k_flags_to_bytes(const int *flag, int n, unsigned char *out) {
 }  // namespace
 
 
+// ---- DistState's lifetime and what fast.hip asks of it (fast_state.hpp) --------------------------------------
+int dist_alloc(mpmhip_ctx *c) {
+  FastState *f = c->fast;
+  DistState *ds = f->ds = new DistState();
+  if (const char *e = getenv("MPMHIP_DIST_FUSED_HALO")) ds->fused_want = atoi(e) != 0;
+  const char *hm = getenv("MPMHIP_DIST_HALO");  // "rccl": keep the halos on ncclSend/ncclRecv; default: peer-mapped buffers
+  ds->link_want = !(hm && !strcmp(hm, "rccl"));
+  return dalloc(c, &ds->pack_done, (size_t)DONE_SHARDS * DONE_STRIDE);
+}
+void dist_free(FastState *f) {
+  DistState *ds = f->ds;
+  if (!ds) return;
+  for (auto &p : ds->peers) {
+    if (p.link_remote) (void)hipIpcCloseMemHandle(p.link_remote);
+    if (p.link_local) (void)hipFree(p.link_local);
+  }
+  if (ds->rccl.comm) (void)ds->rccl.CommDestroy(ds->rccl.comm);
+  delete ds;
+  f->ds = nullptr;
+}
+bool dist_fused_halo_now(const mpmhip_ctx *c) {
+  return c->fast->dist && c->fast->ds->fused_halo && !c->profiling && !c->prof_fused;
+}
+// (the fused halo is decided only where every peer that shares blocks is linked and all fit one table, rccl_rebin: the send table
+// addresses the neighbours' arenas alone)
+void dist_pack_riders(mpmhip_ctx *c, PackArgs &pk) {
+  if (!dist_fused_halo_now(c)) return;
+  const DistState *ds = c->fast->ds;
+  pk.tb = halo_tab(ds->peers.data(), ds->peers.size(), 0, true, !c->movers.empty(), ds->halo_seq, ds->link_on);
+  pk.n_wg = pk.tb.wg_off[pk.tb.n];
+}
+void dist_pack_placed(mpmhip_ctx *c, const LaunchLayout &lay, PackArgs &pk) {
+  if (!dist_fused_halo_now(c)) return;
+  DistState *ds = c->fast->ds;
+  pk.count = 1;
+  pk.done = ds->pack_done;
+  ds->pack_target += (unsigned)lay.n_scatter();
+  pk.target = ds->pack_target;
+}
+
 // ---- multi-GPU entry points --------------------------------------------------------------------------------
 // a context becomes one rank of a sharded run (either transport): the drift look-ahead gets its multi-GPU default
 static void enter_dist_mode(FastState *f) {
@@ -132,7 +254,7 @@ int fast_dist_num_blocks(const mpmhip_ctx *c) { return (int)c->fast->nblocks; }
 int64_t fast_dist_halo_bytes(const mpmhip_ctx *c) {  // bytes this rank sends per substep in the halo exchange (all peers)
   int CH = halo_channels(!c->movers.empty());
   int64_t n = 0;
-  for (auto &p : c->fast->peers) n += (int64_t)(halo_floats(p.n_blocks, CH) * sizeof(float));
+  for (auto &p : c->fast->ds->peers) n += (int64_t)(halo_floats(p.n_blocks, CH) * sizeof(float));
   return n;
 }
 
@@ -141,12 +263,8 @@ int fast_dist_rebin(mpmhip_ctx *c, unsigned char *active_map) {
   int rc;
   if (!c->st_bound || !c->md_bound) return fail(c, MPMHIP_ERR_STATE, "dist_rebin: state/model not bound");
   if (c->caller_dirty && (rc = do_import(c))) return rc;
-  if (!f->dist_keep_cur) {
-    // between substeps the caller's mesh tensors may be gone: bin the body faces from the context's own copy
-    c->cur_pts = c->mesh_points;
-    c->cur_vel = c->mesh_vel;
-    c->cur_f = 0.0f;
-  }
+  // between substeps the caller's mesh tensors may be gone: bin the body faces from the context's own copy
+  if (!f->ds->dist_keep_cur) set_body_view(c, nullptr, nullptr, 0.0f);
   if ((rc = rebin(c))) return rc;
   if (active_map)
     hipLaunchKernelGGL(k_flags_to_bytes, nblk(f->nblocks), TPB, 0, c->stream, f->ab_flag, (int)f->nblocks, active_map);
@@ -156,36 +274,17 @@ int fast_dist_rebin(mpmhip_ctx *c, unsigned char *active_map) {
 int fast_dist_set_peers(mpmhip_ctx *c, int n, const mpmhip_dist_peer *peers) {
   FastState *f = c->fast;
   if (n < 0 || n > 64 || (n > 0 && !peers)) return fail(c, MPMHIP_ERR_INVALID, "dist_set_peers: bad peer list");
-  f->peers.clear();
-  for (int i = 0; i < n; ++i) f->peers.push_back(DistPeer(peers[i]));
+  f->ds->peers.clear();
+  for (int i = 0; i < n; ++i) f->ds->peers.push_back(RcclPeer(peers[i]));
   return MPMHIP_OK;
 }
 
-static inline bool peer_linked(const FastState *f, const DistPeer &p) {
-  return f->link_on && p.link_remote && p.n_blocks <= p.link_cap;
-}
 // halo (send = true: pack into halo_send, false: add halo_recv) for all peers, PEER_TAB per launch
 static void launch_halo(mpmhip_ctx *c, bool send) {
   FastState *f = c->fast;
-  int with_mov = c->movers.empty() ? 0 : 1, CH = halo_channels(with_mov);
-  for (size_t i0 = 0; i0 < f->peers.size(); i0 += PEER_TAB) {
-    HaloTab tb{};
-    tb.with_mov = with_mov;
-    for (size_t i = i0; i < std::min(f->peers.size(), i0 + PEER_TAB); ++i) {
-      const DistPeer &p = f->peers[i];
-      if (!p.n_blocks) continue;
-      int k = tb.n++;
-      tb.blocks[k] = p.blocks; tb.n_blocks[k] = p.n_blocks; tb.buf[k] = send ? p.halo_send : p.halo_recv;
-      if (peer_linked(f, p)) {  // store into / read from the receive arena of this pair instead, flag in the same memory
-        float *arena = send ? p.link_remote : p.link_local;
-        int par = (int)(f->halo_seq & 1u);
-        tb.buf[k] = link_data(arena, par, p.link_cap);
-        tb.sig[k] = link_flag(arena, par);
-        tb.cnt[k] = p.link_cnt;
-      }
-      tb.wg_off[k + 1] = tb.wg_off[k] + (int)nblk(halo_floats(p.n_blocks, CH));
-    }
-    tb.seq = (int)f->halo_seq;
+  const DistState *ds = f->ds;
+  for (size_t i0 = 0; i0 < ds->peers.size(); i0 += PEER_TAB) {
+    const HaloTab tb = halo_tab(ds->peers.data(), ds->peers.size(), i0, send, !c->movers.empty(), ds->halo_seq, ds->link_on);
     if (!tb.n) continue;
     if (send) hipLaunchKernelGGL(k_halo_pack, (unsigned)tb.wg_off[tb.n], TPB, 0, c->stream, tb, f->g);
     else hipLaunchKernelGGL(k_halo_add, (unsigned)tb.wg_off[tb.n], TPB, 0, c->stream, tb, f->g);
@@ -193,17 +292,9 @@ static void launch_halo(mpmhip_ctx *c, bool send) {
 }
 static void launch_ghosts(mpmhip_ctx *c, bool send) {
   FastState *f = c->fast;
-  for (size_t i0 = 0; i0 < f->peers.size(); i0 += PEER_TAB) {
-    GhostTab tb{};
-    for (size_t i = i0; i < std::min(f->peers.size(), i0 + PEER_TAB); ++i) {
-      const DistPeer &p = f->peers[i];
-      int np = send ? p.n_send_p : p.n_recv_p, ne = send ? p.n_send_e : p.n_recv_e;
-      if (np + ne == 0) continue;
-      int k = tb.n++;
-      tb.ids_p[k] = send ? p.send_p : p.recv_p; tb.ids_e[k] = send ? p.send_e : p.recv_e;
-      tb.n_p[k] = np; tb.n_e[k] = ne; tb.buf[k] = send ? p.ghost_send : p.ghost_recv;
-      tb.wg_off[k + 1] = tb.wg_off[k] + (int)nblk((size_t)(np + ne));
-    }
+  const DistState *ds = f->ds;
+  for (size_t i0 = 0; i0 < ds->peers.size(); i0 += PEER_TAB) {
+    const GhostTab tb = ghost_tab(ds->peers.data(), ds->peers.size(), i0, send);
     if (!tb.n) continue;
     if (send) hipLaunchKernelGGL(k_ghost_pack, (unsigned)tb.wg_off[tb.n], TPB, 0, c->stream, tb, f->inv, f->buf[f->cur]);
     else hipLaunchKernelGGL(k_ghost_unpack, (unsigned)tb.wg_off[tb.n], TPB, 0, c->stream, tb, f->inv, f->buf[f->cur]);
@@ -212,43 +303,30 @@ static void launch_ghosts(mpmhip_ctx *c, bool send) {
 
 int fast_dist_phase(mpmhip_ctx *c, int phase, const StepArgs &a) {
   FastState *f = c->fast;
+  DistState *ds = f->ds;
   int rc;
   if (phase == 0) {
-    f->dist_args = a;
+    ds->dist_args = a;
     if ((rc = step_phase_a(c, a))) return rc;
-    const bool fused_halo_now = f->fused_halo && !c->profiling && !c->prof_fused;   // (the pack rode in the p2g launch)
-    if (!fused_halo_now) {
+    if (!dist_fused_halo_now(c)) {     // (else the pack rode in the p2g launch)
       ScopedPhase ph(c, "halo_pack");  // (profiling only) with peer links: the stores into the neighbour's memory + its flag
       launch_halo(c, true);
     }
   } else if (phase == 1) {
-    const bool fused_halo_now = f->fused_halo && !c->profiling && !c->prof_fused;
-    if (!fused_halo_now) {
+    if (!dist_fused_halo_now(c)) {
       ScopedPhase ph(c, "halo_add");   // (profiling only) with peer links: includes the wait for the neighbour's flag
       launch_halo(c, false);
     } else {  // g2p adds the neighbours' shares itself: this substep's receive buffers and flags
-      f->fused_halo_steps += 1;
-      HaloIn &h = f->g.halo;
-      h = HaloIn{};
-      h.slot = f->halo_slot;
-      h.n_peers = (int)f->peers.size();
-      h.seq = (int)f->halo_seq;
-      h.ch = halo_channels(!c->movers.empty());
-      const int par = (int)(f->halo_seq & 1u);
-      for (size_t i = 0; i < f->peers.size(); ++i) {
-        const DistPeer &q = f->peers[i];
-        if (!q.n_blocks || !q.link_local) continue;
-        h.buf[i] = link_data(q.link_local, par, q.link_cap);
-        h.sig[i] = link_flag(q.link_local, par);
-      }
+      ds->fused_halo_steps += 1;
+      f->g.halo = halo_in(ds->peers.data(), ds->peers.size(), ds->halo_slot, !c->movers.empty(), ds->halo_seq);
     }
-    rc = step_phase_b(c, f->dist_args);
+    rc = step_phase_b(c, ds->dist_args);
     f->g.halo.slot = nullptr;
     if (rc) return rc;
     if (!f->ghost_g2p) launch_ghosts(c, true);
   } else {
     if (!f->ghost_g2p) launch_ghosts(c, false);
-    if ((rc = step_phase_c(c, f->dist_args))) return rc;
+    if ((rc = step_phase_c(c, ds->dist_args))) return rc;
   }
   MPM_HIP_CHECK(c, hipGetLastError());
   return MPMHIP_OK;
@@ -282,46 +360,46 @@ int fast_rccl_unique_id(char id[128], std::string &err) {
 
 int fast_rccl_init(mpmhip_ctx *c, int rank, int world, const char id[128]) {
   FastState *f = c->fast;
+  Rccl &r = f->ds->rccl;
   if (world < 1 || rank < 0 || rank >= world) return fail(c, MPMHIP_ERR_INVALID, "rccl_init: bad rank/world");
-  if (!f->rccl.load(c->err)) return MPMHIP_ERR_HIP;
+  if (!r.load(c->err)) return MPMHIP_ERR_HIP;
   ncclUniqueId uid;
   memcpy(&uid, id, 128);
-  MPM_NCCL_CHECK(c, f->rccl, f->rccl.CommInitRank(&f->rccl.comm, world, uid, rank));
-  f->rccl.rank = rank;
-  f->rccl.world = world;
+  MPM_NCCL_CHECK(c, r, r.CommInitRank(&r.comm, world, uid, rank));
+  r.rank = rank;
+  r.world = world;
   enter_dist_mode(f);
-  const char *hm = getenv("MPMHIP_DIST_HALO");  // "rccl": keep the halos on ncclSend/ncclRecv; default: peer-mapped buffers
-  f->link_want = !(hm && !strcmp(hm, "rccl"));
-  int rc;
-  if ((rc = dalloc(c, &f->map_all, (size_t)world * f->nblocks))) return rc;
-  return MPMHIP_OK;
+  return dalloc(c, &f->ds->map_all, (size_t)world * f->nblocks);
 }
 
 int fast_rccl_set_ghosts(mpmhip_ctx *c, int n, const int32_t *ranks, const int32_t *nsp, const int32_t *const *sp,
                          const int32_t *nrp, const int32_t *const *rp, const int32_t *nse, const int32_t *const *se,
                          const int32_t *nre, const int32_t *const *re) {
   FastState *f = c->fast;
-  if (!f->rccl.comm) return fail(c, MPMHIP_ERR_STATE, "rccl_set_ghosts: call mpmhip_rccl_init first");
+  DistState *ds = f->ds;
+  if (!ds->rccl.comm) return fail(c, MPMHIP_ERR_STATE, "rccl_set_ghosts: call mpmhip_rccl_init first");
   // one peer slot per other rank (shared blocks may exist without ghosts, e.g. traditional particles only)
-  f->rpeers.clear();
-  for (int q = 0; q < f->rccl.world; ++q) {
-    if (q == f->rccl.rank) continue;
+  ds->peers.clear();
+  for (int q = 0; q < ds->rccl.world; ++q) {
+    if (q == ds->rccl.rank) continue;
     RcclPeer p;
     p.rank = q;
     int rc;
     if ((rc = dalloc(c, &p.flag, f->nblocks))) return rc;
     if ((rc = dalloc(c, &p.index, f->nblocks))) return rc;
-    f->rpeers.push_back(p);
+    ds->peers.push_back(p);
   }
-  auto up = [&](int **dst, const int32_t *src, int cnt) -> int {
-    int rc = dalloc(c, dst, (size_t)std::max(cnt, 1), false);
+  auto up = [&](const int32_t **dst, const int32_t *src, int cnt) -> int {
+    int *dev = nullptr;
+    int rc = dalloc(c, &dev, (size_t)std::max(cnt, 1), false);
     if (rc) return rc;
-    if (cnt) MPM_HIP_CHECK(c, hipMemcpy(*dst, src, (size_t)cnt * sizeof(int), hipMemcpyHostToDevice));
+    if (cnt) MPM_HIP_CHECK(c, hipMemcpy(dev, src, (size_t)cnt * sizeof(int), hipMemcpyHostToDevice));
+    *dst = dev;
     return MPMHIP_OK;
   };
   for (int i = 0; i < n; ++i) {
     RcclPeer *p = nullptr;
-    for (auto &q : f->rpeers) if (q.rank == ranks[i]) p = &q;
+    for (auto &q : ds->peers) if (q.rank == ranks[i]) p = &q;
     if (!p) return fail(c, MPMHIP_ERR_INVALID, "rccl_set_ghosts: bad peer rank");
     int rc;
     p->n_send_p = nsp[i]; p->n_recv_p = nrp[i]; p->n_send_e = nse[i]; p->n_recv_e = nre[i];
@@ -337,7 +415,7 @@ int fast_rccl_set_ghosts(mpmhip_ctx *c, int n, const int32_t *ranks, const int32
 // max over the ranks of CNT_LINK_VOTE (1: some link of this rank does not work), read back into h_pin[PIN_LINK_VOTE]
 static int reduce_vote(mpmhip_ctx *c) {
   FastState *f = c->fast;
-  Rccl &r = f->rccl;
+  Rccl &r = f->ds->rccl;
   int *vote = f->g.counters + CNT_LINK_VOTE, *vote_all = f->g.counters + CNT_LINK_VOTE_ALL;
   MPM_NCCL_CHECK(c, r, r.AllReduce(vote, vote_all, 1, ncclInt32, ncclMax, r.comm, c->stream));
   MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + PIN_LINK_VOTE, vote_all, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -354,13 +432,14 @@ static int reduce_vote(mpmhip_ctx *c) {
 // blocks only later, or share more than link_cap of them, use send/recv for that interval (both sides see the same count).
 static int rccl_link_setup(mpmhip_ctx *c) {
   FastState *f = c->fast;
-  Rccl &r = f->rccl;
+  DistState *ds = f->ds;
+  Rccl &r = ds->rccl;
   hipStream_t s = c->stream;
   int rc, bad = 0;
-  f->link_decided = true;
-  std::vector<hipIpcMemHandle_t> mine(f->rpeers.size()), theirs(f->rpeers.size());
-  for (size_t i = 0; i < f->rpeers.size(); ++i) {
-    RcclPeer &p = f->rpeers[i];
+  ds->link_decided = true;
+  std::vector<hipIpcMemHandle_t> mine(ds->peers.size()), theirs(ds->peers.size());
+  for (size_t i = 0; i < ds->peers.size(); ++i) {
+    RcclPeer &p = ds->peers[i];
     memset(&mine[i], 0, sizeof(hipIpcMemHandle_t));
     if (!p.n_blocks) continue;
     if ((rc = dalloc(c, &p.link_cnt, 1))) return rc;
@@ -380,26 +459,26 @@ static int rccl_link_setup(mpmhip_ctx *c) {
   (void)hipGetDevice(&my_dev);
   if (hipDeviceGetPCIBusId(my_bus, (int)sizeof my_bus, my_dev) != hipSuccess) my_bus[0] = 0;
   (void)hipGetLastError();
-  std::vector<std::array<char, 96>> msg_out(f->rpeers.size()), msg_in(f->rpeers.size());
-  for (size_t i = 0; i < f->rpeers.size(); ++i) {
+  std::vector<std::array<char, 96>> msg_out(ds->peers.size()), msg_in(ds->peers.size());
+  for (size_t i = 0; i < ds->peers.size(); ++i) {
     memcpy(msg_out[i].data(), &mine[i], 64);
     memcpy(msg_out[i].data() + 64, my_bus, 32);
-    if (f->rpeers[i].n_blocks) MPM_HIP_CHECK(c, hipMemcpyAsync(f->rpeers[i].hbuf, msg_out[i].data(), 96, hipMemcpyHostToDevice, s));
+    if (ds->peers[i].n_blocks) MPM_HIP_CHECK(c, hipMemcpyAsync(ds->peers[i].hbuf, msg_out[i].data(), 96, hipMemcpyHostToDevice, s));
   }
   static_assert(sizeof(hipIpcMemHandle_t) == 64, "HIP IPC handle size");
   MPM_NCCL_CHECK(c, r, r.GroupStart());
-  for (auto &p : f->rpeers) {
+  for (auto &p : ds->peers) {
     if (!p.n_blocks) continue;
     MPM_NCCL_CHECK(c, r, r.Send(p.hbuf, 96, ncclUint8, p.rank, r.comm, s));
     MPM_NCCL_CHECK(c, r, r.Recv(p.hbuf + 128, 96, ncclUint8, p.rank, r.comm, s));
   }
   MPM_NCCL_CHECK(c, r, r.GroupEnd());
-  for (size_t i = 0; i < f->rpeers.size(); ++i)
-    if (f->rpeers[i].n_blocks) MPM_HIP_CHECK(c, hipMemcpyAsync(msg_in[i].data(), f->rpeers[i].hbuf + 128, 96, hipMemcpyDeviceToHost, s));
+  for (size_t i = 0; i < ds->peers.size(); ++i)
+    if (ds->peers[i].n_blocks) MPM_HIP_CHECK(c, hipMemcpyAsync(msg_in[i].data(), ds->peers[i].hbuf + 128, 96, hipMemcpyDeviceToHost, s));
   MPM_HIP_CHECK(c, hipStreamSynchronize(s));
   const bool verbose = getenv("MPMHIP_VERBOSE") != nullptr;
-  for (size_t i = 0; i < f->rpeers.size(); ++i) {
-    RcclPeer &p = f->rpeers[i];
+  for (size_t i = 0; i < ds->peers.size(); ++i) {
+    RcclPeer &p = ds->peers[i];
     if (!p.n_blocks) continue;
     static const hipIpcMemHandle_t none{};
     memcpy(&theirs[i], msg_in[i].data(), 64);
@@ -441,14 +520,14 @@ static int rccl_link_setup(mpmhip_ctx *c) {
   if (f->h_pin[PIN_LINK_VOTE] == 0) {
     MPM_HIP_CHECK(c, hipMemsetAsync(f->g.counters + CNT_LINK_TIMEOUT, 0, 2 * sizeof(int), s));  // (TIMEOUT and BAD)
     for (int round = 0; round < 4; ++round) {
-      int seq = (int)++f->halo_seq, par = seq & 1;
+      const int seq = (int)++ds->halo_seq, par = halo_parity(ds->halo_seq);
       auto n_test = [](const RcclPeer &p) { return (int)std::min<size_t>(halo_floats(p.link_cap, HALO_CHANNELS_MAX), (size_t)1 << 16); };
-      for (auto &p : f->rpeers) {
+      for (auto &p : ds->peers) {
         if (!p.link_remote) continue;
         hipLaunchKernelGGL(k_link_ping, 16, TPB, 0, s, (unsigned *)link_data(p.link_remote, par, p.link_cap), n_test(p), p.link_cnt,
                            link_flag(p.link_remote, par), seq);
       }
-      for (auto &p : f->rpeers) {
+      for (auto &p : ds->peers) {
         if (!p.link_remote) continue;
         hipLaunchKernelGGL(k_link_check, 16, TPB, 0, s, (const unsigned *)link_data(p.link_local, par, p.link_cap), n_test(p),
                            (const int *)link_flag(p.link_local, par), seq, f->g.counters);
@@ -458,70 +537,68 @@ static int rccl_link_setup(mpmhip_ctx *c) {
     if ((rc = reduce_vote(c))) return rc;
     MPM_HIP_CHECK(c, hipMemsetAsync(f->g.counters + CNT_LINK_TIMEOUT, 0, 2 * sizeof(int), s));
   }
-  f->link_on = f->h_pin[PIN_LINK_VOTE] == 0;
+  ds->link_on = f->h_pin[PIN_LINK_VOTE] == 0;
   if (getenv("MPMHIP_VERBOSE"))
-    fprintf(stderr, "[mpmhip] rank %d: halo transport %s\n", r.rank, f->link_on ? "peer-mapped buffers" : "ncclSend/ncclRecv");
+    fprintf(stderr, "[mpmhip] rank %d: halo transport %s\n", r.rank, ds->link_on ? "peer-mapped buffers" : "ncclSend/ncclRecv");
   return MPMHIP_OK;
 }
 
 static int rccl_rebin(mpmhip_ctx *c) {
   FastState *f = c->fast;
-  Rccl &r = f->rccl;
+  DistState *ds = f->ds;
+  Rccl &r = ds->rccl;
   hipStream_t s = c->stream;
   int rc, nb = (int)f->nblocks;
-  unsigned char *mine = f->map_all + (size_t)r.rank * f->nblocks;
+  unsigned char *mine = ds->map_all + (size_t)r.rank * f->nblocks;
   if ((rc = fast_dist_rebin(c, mine))) return rc;
-  MPM_NCCL_CHECK(c, r, r.AllGather(mine, f->map_all, f->nblocks, ncclUint8, r.comm, s));
-  f->peers.clear();
-  for (auto &p : f->rpeers) {
-    hipLaunchKernelGGL(k_shared_flags, nblk(nb), TPB, 0, s, mine, f->map_all + (size_t)p.rank * f->nblocks, nb, p.flag);
+  MPM_NCCL_CHECK(c, r, r.AllGather(mine, ds->map_all, f->nblocks, ncclUint8, r.comm, s));
+  for (auto &p : ds->peers) {
+    hipLaunchKernelGGL(k_shared_flags, nblk(nb), TPB, 0, s, mine, ds->map_all + (size_t)p.rank * f->nblocks, nb, p.flag);
     // index[] and blocks[] in one go (the re-sort's flag compaction), total read back; too many for blocks[]: grown, and again
-    if ((rc = compact_shared_blocks(c, p.flag, nb, p.index, p.blocks, p.cap_blocks, &p.n_blocks))) return rc;
+    if ((rc = compact_shared_blocks(c, p.flag, nb, p.index, p.own_blocks(), p.cap_blocks, &p.n_blocks))) return rc;
     if (p.n_blocks > p.cap_blocks) {
-      int cap = std::max(p.n_blocks + p.n_blocks / 2, 256);
-      if ((rc = dalloc(c, &p.blocks, (size_t)cap, false))) return rc;
+      int cap = std::max(p.n_blocks + p.n_blocks / 2, 256), *grown = nullptr;
+      if ((rc = dalloc(c, &grown, (size_t)cap, false))) return rc;
+      p.blocks = grown;
       if ((rc = dalloc(c, &p.halo_send, halo_floats(cap, HALO_CHANNELS_MAX), false))) return rc;   // (sized for the wider record)
       if ((rc = dalloc(c, &p.halo_recv, halo_floats(cap, HALO_CHANNELS_MAX), false))) return rc;
       p.cap_blocks = cap;
-      if ((rc = compact_shared_blocks(c, p.flag, nb, p.index, p.blocks, p.cap_blocks, nullptr))) return rc;
+      if ((rc = compact_shared_blocks(c, p.flag, nb, p.index, p.own_blocks(), p.cap_blocks, nullptr))) return rc;
     }
   }
-  if (f->link_want && !f->link_decided && (rc = rccl_link_setup(c))) return rc;   // (first re-sort: the links come up here)
-  for (auto &p : f->rpeers) f->peers.push_back(p.view());
+  if (ds->link_want && !ds->link_decided && (rc = rccl_link_setup(c))) return rc;   // (first re-sort: the links come up here)
   // fused halo for this interval?
-  f->fused_halo = false;
-  if (f->fused_want && f->link_on && f->fuse_grid && f->peers.size() <= (size_t)PEER_TAB) {
+  ds->fused_halo = false;
+  if (ds->fused_want && ds->link_on && f->fuse_grid && ds->peers.size() <= (size_t)PEER_TAB) {
     bool all = true, any = false;
-    for (auto &q : f->peers)
-      if (q.n_blocks) { any = true; all = all && peer_linked(f, q); }
+    for (auto &q : ds->peers)
+      if (q.n_blocks) { any = true; all = all && peer_linked(ds->link_on, q); }
     if (all && any) {
-      if (!f->halo_slot) {
-        if ((rc = dalloc(c, &f->halo_slot, f->nblocks + 1, false))) return rc;
-        f->halo_multi = f->halo_slot + f->nblocks;
+      if (!ds->halo_slot) {
+        if ((rc = dalloc(c, &ds->halo_slot, f->nblocks + 1, false))) return rc;
+        ds->halo_multi = ds->halo_slot + f->nblocks;
       }
-      MPM_HIP_CHECK(c, hipMemsetAsync(f->halo_slot, 0xff, f->nblocks * sizeof(int), s));
-      MPM_HIP_CHECK(c, hipMemsetAsync(f->halo_multi, 0, sizeof(int), s));
-      for (size_t i = 0; i < f->peers.size(); ++i)
-        if (f->peers[i].n_blocks)
-          hipLaunchKernelGGL(k_halo_slots, nblk(nb), TPB, 0, s, f->rpeers[i].flag, f->rpeers[i].index, nb, (int)i, f->halo_slot, f->halo_multi);
-      MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + PIN_HALO_MULTI, f->halo_multi, sizeof(int), hipMemcpyDeviceToHost, s));
+      MPM_HIP_CHECK(c, hipMemsetAsync(ds->halo_slot, 0xff, f->nblocks * sizeof(int), s));
+      MPM_HIP_CHECK(c, hipMemsetAsync(ds->halo_multi, 0, sizeof(int), s));
+      for (size_t i = 0; i < ds->peers.size(); ++i)
+        if (ds->peers[i].n_blocks)
+          hipLaunchKernelGGL(k_halo_slots, nblk(nb), TPB, 0, s, ds->peers[i].flag, ds->peers[i].index, nb, (int)i, ds->halo_slot, ds->halo_multi);
+      MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + PIN_HALO_MULTI, ds->halo_multi, sizeof(int), hipMemcpyDeviceToHost, s));
       MPM_HIP_CHECK(c, hipStreamSynchronize(s));
-      f->fused_halo = f->h_pin[PIN_HALO_MULTI] == 0;
+      ds->fused_halo = f->h_pin[PIN_HALO_MULTI] == 0;
     }
   }
   return MPMHIP_OK;
 }
 
-// f->peers[i] corresponds to f->rpeers[i]
 static int rccl_exchange(mpmhip_ctx *c, bool halo) {
-  FastState *f = c->fast;
-  Rccl &r = f->rccl;
+  const DistState *ds = c->fast->ds;
+  const Rccl &r = ds->rccl;
   int CH = halo_channels(!c->movers.empty());
   bool open = false;
-  for (size_t i = 0; i < f->peers.size(); ++i) {
-    const DistPeer &p = f->peers[i];
-    int peer = f->rpeers[i].rank;
-    if (halo && peer_linked(f, p)) continue;  // went through the pair's link (k_halo_pack / k_halo_add)
+  for (const RcclPeer &p : ds->peers) {
+    const int peer = p.rank;
+    if (halo && peer_linked(ds->link_on, p)) continue;  // went through the pair's link (k_halo_pack / k_halo_add)
     size_t ns = halo ? halo_floats(p.n_blocks, CH) : ghost_floats(p.n_send_p, p.n_send_e);
     size_t nr = halo ? halo_floats(p.n_blocks, CH) : ghost_floats(p.n_recv_p, p.n_recv_e);
     if ((ns || nr) && !open) { MPM_NCCL_CHECK(c, r, r.GroupStart()); open = true; }
@@ -535,7 +612,8 @@ static int rccl_exchange(mpmhip_ctx *c, bool halo) {
 int fast_rccl_steps(mpmhip_ctx *c, float dt, int n, int64_t step_index, int rebin_interval, const float *mesh_x,
                     const float *mesh_v, const float *jt, int n_jt, const float *jv, const float *jf) {
   FastState *f = c->fast;
-  if (!f->rccl.comm) return fail(c, MPMHIP_ERR_STATE, "rccl_steps: call mpmhip_rccl_init first");
+  DistState *ds = f->ds;
+  if (!ds->rccl.comm) return fail(c, MPMHIP_ERR_STATE, "rccl_steps: call mpmhip_rccl_init first");
   // rebin_interval > 0: every rank re-sorts at substeps that are multiples of it.  <= 0: when any rank's early-warning
   // drift flag is up (the single-GPU policy made collective), at the latest every 256 (or -rebin_interval) substeps.
   const bool adaptive = rebin_interval <= 0;
@@ -545,46 +623,45 @@ int fast_rccl_steps(mpmhip_ctx *c, float dt, int n, int64_t step_index, int rebi
   for (int k = 0; k < n; ++k) {
     int64_t idx = step_index + k;
     StepArgs a{dt, mesh_x, mesh_v, (float)((double)dt * (double)idx), true, jt, jt ? n_jt : 0, jv, jf};
-    c->cur_pts = a.mesh_x ? a.mesh_x : c->mesh_points;
-    c->cur_vel = a.mesh_v ? a.mesh_v : c->mesh_vel;
-    c->cur_f = (a.mesh_x && a.mesh_v) ? a.mesh_f : 0.0f;
-    if (adaptive && f->dflag_in_flight && idx >= f->dflag_check_at) {
+    set_body_view(c, a.mesh_x, a.mesh_v, a.mesh_f);
+    if (adaptive && ds->dflag_in_flight && idx >= ds->dflag_check_at) {
       // posted by k_post_flag: wait for THIS reduction's sequence number, then read its value
-      for (long spins = 0; (unsigned)f->h_sig[SIG_DSEQ] != f->dflag_seq; ++spins) {
+      for (long spins = 0; (unsigned)f->h_sig[SIG_DSEQ] != ds->dflag_seq; ++spins) {
         if ((spins & 0x3ff) == 0x3ff) {
           hipError_t e = hipStreamQuery(c->stream);
-          if (e == hipSuccess && (unsigned)f->h_sig[SIG_DSEQ] != f->dflag_seq)
+          if (e == hipSuccess && (unsigned)f->h_sig[SIG_DSEQ] != ds->dflag_seq)
             return fail(c, MPMHIP_ERR_HIP, "rccl_steps: the reduced drift flag never reached host memory");
           if (e != hipSuccess && e != hipErrorNotReady) MPM_HIP_CHECK(c, e);
         }
         std::this_thread::yield();
       }
       std::atomic_thread_fence(std::memory_order_acquire);
-      if (f->h_sig[SIG_DFLAG]) f->dist_resort = true;
-      f->dflag_in_flight = false;
+      if (f->h_sig[SIG_DFLAG]) ds->dist_resort = true;
+      ds->dflag_in_flight = false;
     }
-    bool due = adaptive ? (f->dist_resort || f->dist_since >= cap || !f->rccl_sorted) : (idx % cap == 0);
+    bool due = adaptive ? (ds->dist_resort || ds->dist_since >= cap || !ds->rccl_sorted) : (idx % cap == 0);
     if (due || c->caller_dirty) {
-      if (f->ghost_g2p && f->have_order && !c->caller_dirty && !f->peers.empty()) {  // owners -> copies, then re-sort
+      // owners -> copies, then re-sort (not before the first collective re-sort: the peers have their ghost lists, no order yet)
+      if (f->ghost_g2p && f->have_order && !c->caller_dirty && ds->rccl_sorted && !ds->peers.empty()) {
         if ((rc = fast_dist_ghosts(c, 1))) return rc;
         if ((rc = rccl_exchange(c, false))) return rc;
         if ((rc = fast_dist_ghosts(c, 0))) return rc;
       }
       if (adaptive && f->true_since_rebin > 0)  // predictive sort: aim at the middle of the next interval
         f->lead_steps = std::min(std::max(0.5f * (float)f->true_since_rebin, 4.0f), 48.0f);
-      f->dist_keep_cur = true;
+      ds->dist_keep_cur = true;
       rc = rccl_rebin(c);
-      f->dist_keep_cur = false;
+      ds->dist_keep_cur = false;
       if (rc) return rc;
       f->true_since_rebin = 0;
-      f->dist_since = 0;
-      f->dist_resort = false;
-      f->rccl_sorted = true;
+      ds->dist_since = 0;
+      ds->dist_resort = false;
+      ds->rccl_sorted = true;
       // a reduction issued before this re-sort speaks about the old order: drop it (every rank does; the next poll waits for a
       // newer sequence number)
-      f->dflag_in_flight = false;
+      ds->dflag_in_flight = false;
     }
-    f->halo_seq += 1;
+    ds->halo_seq += 1;
     if ((rc = fast_dist_phase(c, 0, a))) return rc;
     {
       ScopedPhase ph(c, "halo_exchange");  // (profiling only: the ncclSend/ncclRecv group between the pack and the add kernel)
@@ -593,27 +670,26 @@ int fast_rccl_steps(mpmhip_ctx *c, float dt, int n, int64_t step_index, int rebi
     if ((rc = fast_dist_phase(c, 1, a))) return rc;
     if (!f->ghost_g2p && (rc = rccl_exchange(c, false))) return rc;
     if ((rc = fast_dist_phase(c, 2, a))) return rc;
-    c->time = c->time + c->time_inc(dt);
-    c->substeps += 1;
-    f->dist_since += 1;
-    if (adaptive && !f->dflag_in_flight && f->dist_since % DIST_POLL == 0) {
-      MPM_NCCL_CHECK(c, f->rccl, f->rccl.AllReduce(f->g.counters + CNT_DRIFT, f->g.counters + CNT_DRIFT_ALL, 1, ncclInt32, ncclMax,
-                                                   f->rccl.comm, c->stream));
+    advance_time(c, dt);
+    ds->dist_since += 1;
+    if (adaptive && !ds->dflag_in_flight && ds->dist_since % DIST_POLL == 0) {
+      MPM_NCCL_CHECK(c, ds->rccl, ds->rccl.AllReduce(f->g.counters + CNT_DRIFT, f->g.counters + CNT_DRIFT_ALL, 1, ncclInt32, ncclMax,
+                                                   ds->rccl.comm, c->stream));
       // no copy + event on the stream (each costs an idle queue, see fast_step): one thread posts the result
-      hipLaunchKernelGGL(k_post_flag, 1, 1, 0, c->stream, f->g.counters + CNT_DRIFT_ALL, f->g.host_sig, (int)++f->dflag_seq);
-      f->dflag_in_flight = true;
-      f->dflag_check_at = idx + 1 + DIST_LAG;
+      hipLaunchKernelGGL(k_post_flag, 1, 1, 0, c->stream, f->g.counters + CNT_DRIFT_ALL, f->g.host_sig, (int)++ds->dflag_seq);
+      ds->dflag_in_flight = true;
+      ds->dflag_check_at = idx + 1 + DIST_LAG;
     }
   }
-  if (f->link_on) {  // a wait that ran into its wall-clock bound computed with an incomplete halo: fail the call
+  if (ds->link_on) {  // a wait that ran into its wall-clock bound computed with an incomplete halo: fail the call
     MPM_HIP_CHECK(c, hipMemcpyAsync(f->h_pin + PIN_LINK_TIMEOUT, f->g.counters + CNT_LINK_TIMEOUT, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     MPM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
     if (f->h_pin[PIN_LINK_TIMEOUT]) return fail(c, MPMHIP_ERR_HIP, "rccl_steps: a peer-mapped halo never arrived (flag wait timed out)");
   }
   return MPMHIP_OK;
 }
-int fast_dist_halo_transport(const mpmhip_ctx *c) { return c->fast->link_on ? 1 : 0; }
-int64_t fast_dist_fused_halo_steps(const mpmhip_ctx *c) { return c->fast->fused_halo_steps; }
+int fast_dist_halo_transport(const mpmhip_ctx *c) { return c->fast->ds->link_on ? 1 : 0; }
+int64_t fast_dist_fused_halo_steps(const mpmhip_ctx *c) { return c->fast->ds->fused_halo_steps; }
 
 // the drift flag of this rank (set by the kernels when a particle is about to leave its tile margin); synchronous
 int fast_dist_drift_flag(mpmhip_ctx *c, int32_t *out) {

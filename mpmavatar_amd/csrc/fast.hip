@@ -276,8 +276,9 @@ void materialize_grid(mpmhip_ctx *c, bool count) {
 }
 
 
-// Every environment switch the context reads at creation, in one place (DESIGN.md section 10 lists them, and the ones resort.hip and
-// dist.hip read later, at run time).  Defaults that depend on the scene are set here too, in front of their switch.
+// Every environment switch the context reads at creation, in one place but for the two of the multi-GPU exchange (dist_alloc, dist.hip).
+// DESIGN.md section 10 lists them, and the ones resort.hip and dist.hip read later, at run time.  Defaults that depend on the scene are
+// set here too, in front of their switch.
 static void read_switches(const mpmhip_config &cfg, FastState *f) {
   int cell_bits = f->blk_bits_plain + 8 + 2 + 2 <= 32 ? 8 : 6;  // 8: predictive sort (see make_key)
   if (const char *e = getenv("MPMHIP_PREDICTIVE_SORT")) if (atoi(e) == 0) cell_bits = 6;
@@ -298,7 +299,6 @@ static void read_switches(const mpmhip_config &cfg, FastState *f) {
   f->g2p_two_pass = cfg.n_particles - cfg.n_elements - cfg.n_vertices == 0;
   if (const char *e = getenv("MPMHIP_G2P_TWO_PASS")) f->g2p_two_pass = atoi(e) != 0;
   if (const char *e = getenv("MPMHIP_FUSE_TRAD")) f->fuse_trad = atoi(e) != 0;
-  if (const char *e = getenv("MPMHIP_DIST_FUSED_HALO")) f->fused_want = atoi(e) != 0;
   // p2g's first round staggered by wave slot -- 2 x 1024 cycles per step, 5 groups, the first 1,280 workgroups -- where the launch is
   // more than two rounds of workgroups (decided per launch in step_phase_a): the headline scene +1.1 % at t = 0 and draped (round 4,
   // three alternating runs: 16.06-16.08 k -> 16.21-16.29 k; round 3 had measured the same and left it off because a launch of less
@@ -345,7 +345,7 @@ int fast_init(mpmhip_ctx *c) {
   if ((rc = f->acc.allocate(c, &f->g, f->nblocks, d.n_e == 0 && d.n_v == 0 && d.n_t > 0))) return rc;
   if ((rc = dalloc(c, &f->g.vout, f->nblocks * GCH_VOUT * 64))) return rc;
   if ((rc = dalloc(c, &f->g.counters, CNT_N))) return rc;
-  if ((rc = dalloc(c, &f->pack_done, (size_t)DONE_SHARDS * DONE_STRIDE))) return rc;
+  if ((rc = dist_alloc(c))) return rc;
   if ((rc = resort_alloc(c))) return rc;
   MPM_HIP_CHECK(c, hipHostMalloc((void **)&f->h_pin, PIN_N * sizeof(int), hipHostMallocDefault));
   int *hs = nullptr, *ds = nullptr;
@@ -360,11 +360,7 @@ int fast_init(mpmhip_ctx *c) {
 void fast_destroy(mpmhip_ctx *c) {
   FastState *f = c->fast;
   if (!f) return;
-  for (auto &p : f->rpeers) {
-    if (p.link_remote) (void)hipIpcCloseMemHandle(p.link_remote);
-    if (p.link_local) (void)hipFree(p.link_local);
-  }
-  if (f->rccl.comm) (void)f->rccl.CommDestroy(f->rccl.comm);
+  dist_free(f);
   for (void *p : f->allocs) (void)hipFree(p);
   if (f->h_pin) (void)hipHostFree(f->h_pin);
   if (f->h_sig) (void)hipHostFree((void *)f->h_sig);
@@ -556,31 +552,10 @@ static RiderPlan plan_riders(mpmhip_ctx *c, const StepArgs &a) {
   p.split_splat = f->split_splat && has_col && n_fbins > 0 && d.n_e > 0 && f->elem_pending && !c->profiling && !f->dist &&
                   f->n_chunks <= f->split_splat_max_chunks && !(MPMHIP_DEBUG && f->g.dbg);
   sa.splat_passes = p.split_splat ? 2 : 3;
-  const bool fused_halo_now = f->dist && f->fused_halo && !c->profiling && !c->prof_fused;
-  if (fused_halo_now) {  // (multi-GPU) the halo pack rides in this launch, behind the clearing workgroups: see PackArgs
-    HaloTab &tb = sa.pack.tb;
-    tb.with_mov = c->movers.empty() ? 0 : 1;
-    const int CH = halo_channels(tb.with_mov), par = (int)(f->halo_seq & 1u);
-    for (auto &q : f->peers) {
-      if (!q.n_blocks) continue;
-      int k = tb.n++;
-      tb.blocks[k] = q.blocks; tb.n_blocks[k] = q.n_blocks;
-      tb.buf[k] = link_data(q.link_remote, par, q.link_cap);
-      tb.sig[k] = link_flag(q.link_remote, par);
-      tb.cnt[k] = q.link_cnt;
-      tb.wg_off[k + 1] = tb.wg_off[k] + (int)((halo_floats(q.n_blocks, CH) + PT - 1) / PT);
-    }
-    tb.seq = (int)f->halo_seq;
-    sa.pack.n_wg = tb.wg_off[tb.n];
-  }
+  dist_pack_riders(c, sa.pack);  // (multi-GPU) the halo pack rides in this launch, behind the clearing workgroups: see PackArgs
   p.lay = launch_layout(n_fbins, n_joint, f->n_chunks, sa.z.n_wg, sa.pack.n_wg);
   set_layout(sa, p.lay);
-  if (fused_halo_now) {
-    sa.pack.count = 1;
-    sa.pack.done = f->pack_done;
-    f->pack_target += (unsigned)p.lay.n_scatter();
-    sa.pack.target = f->pack_target;
-  }
+  dist_pack_placed(c, p.lay, sa.pack);
   return p;
 }
 static void issue_stress(mpmhip_ctx *c, const RiderPlan &p, float dt) {

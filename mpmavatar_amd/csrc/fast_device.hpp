@@ -19,6 +19,7 @@
 
 #include "bc.hpp"
 #include "ctx.hpp"
+#include "halo_tables.hpp"
 #include "launch_layout.hpp"
 #include "mpm_math.hpp"
 
@@ -36,6 +37,7 @@ constexpr int PT = CHUNK;      // threads of those workgroups (and of the extra 
 constexpr int TILE = 8;        // tile edge in nodes: block (4) + 1 below + 3 above
 constexpr int TILE3 = TILE * TILE * TILE;
 inline unsigned nblk(size_t n) { return n ? (unsigned)((n + TPB - 1) / TPB) : 1u; }  // never an empty grid: kernels bound-check
+static_assert(TPB == TAB_WG && PT == TAB_WG, "the exchange tables count workgroups of TAB_WG threads (halo_tables.hpp)");
 
 // Kernel ablation switches and the per-workgroup timeline exist only in builds with -DMPMHIP_DEBUG=1
 // (tools/build_variants.py dbg:-DMPMHIP_DEBUG=1, selected with MPMHIP_LIB): the production kernels carry neither the
@@ -301,17 +303,6 @@ static_assert(CNT_NCOL + 1 == CNT_NMOV && CNT_LINK_TIMEOUT + 1 == CNT_LINK_BAD &
               CNT_MMIN + 1 == CNT_MMAX && CNT_MMAX + 1 == CNT_NSEL, "counter slots that are copied or cleared as one range");
 static_assert(CNT_ACTIVE < CNT_STATS_N && CNT_BODY_MOVES < CNT_PAR0 && CNT_PAR0 + 4 <= CNT_MMIN && CNT_NSEL < CNT_N, "counter layout");
 
-// Fused halo add (multi-GPU, peer-mapped halos): k_g2p<.., HALO = true> adds the neighbour rank's contribution to a shared
-// block while it stages its tile -- own accumulator + the value the neighbour's pack stored into this rank's arena -- instead
-// of a separate add kernel between p2g and g2p.  slot == nullptr: off.
-constexpr int PEER_TAB = 8;
-struct HaloIn {
-  const int *slot;             // [blocks] -1, or (peer << 24) | index of the block in that peer's shared-block list
-  const float *buf[PEER_TAB];  // this substep's receive buffer of each peer (arena of parity halo_seq & 1)
-  const int *sig[PEER_TAB];    // its flag: reaches `seq` when the neighbour's pack of this substep has landed
-  int n_peers, seq, ch;        // ch = 4 (m, momentum) or 8 (+ mover channels)
-};
-
 struct GridPtrs {
   float *mv;        // [block][4][64]: m, momentum xyz
   float *vout;      // [block][4][64]: v_out xyz, m (copy kept for introspection)
@@ -573,28 +564,7 @@ struct ChunkRec {
 // as one workgroup the kernel is a chain of memory latencies, and with one block after the other per thread it took 19-25 us.
 constexpr int BC_R = 4;
 
-// ---- multi-GPU exchange helpers (mpmavatar_amd/dist.py drives them) ---------------------------------------
-// halo: the (m, momentum) and mover channels of the grid blocks two ranks both have on their active lists
-// One launch serves up to PEER_TAB neighbours: workgroups [wg_off[p], wg_off[p+1]) belong to peer p.
-struct HaloTab {
-  int n, with_mov;
-  int wg_off[PEER_TAB + 1];
-  const int *blocks[PEER_TAB];
-  int n_blocks[PEER_TAB];
-  float *buf[PEER_TAB];
-  // peer-mapped halos (see "peer links" below): pack stores straight into the neighbour's receive buffer and the last
-  // workgroup raises sig (a flag in the neighbour's memory) to seq; add waits for its own flag to reach seq.  null: none
-  int *sig[PEER_TAB];
-  int *cnt[PEER_TAB];
-  int seq;
-};
-struct GhostTab {
-  int n;
-  int wg_off[PEER_TAB + 1];
-  const int *ids_p[PEER_TAB], *ids_e[PEER_TAB];
-  int n_p[PEER_TAB], n_e[PEER_TAB];
-  float *buf[PEER_TAB];
-};
+// ---- multi-GPU exchange helpers: the tables (HaloTab, GhostTab, HaloIn) are halo_tables.hpp's -------------
 template <class Tab>
 __device__ __forceinline__ int tab_peer(const Tab &t, int wg) {
   int p = 0;

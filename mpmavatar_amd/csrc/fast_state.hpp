@@ -8,95 +8,6 @@ namespace mpm {
 // ================================================================================================
 // host side
 // ================================================================================================
-struct DistPeer : mpmhip_dist_peer {  // the ABI's peer record (shared blocks, halo buffers, ghost lists) plus the pair's link
-  DistPeer() : mpmhip_dist_peer{} {}
-  explicit DistPeer(const mpmhip_dist_peer &p) : mpmhip_dist_peer(p) {}
-  // peer link (in-library loop only): this rank's receive arena and the neighbour's, mapped; see rccl_link_setup
-  float *link_local = nullptr, *link_remote = nullptr;
-  int link_cap = 0;
-  int *link_cnt = nullptr;
-};
-
-struct Rccl {  // entry points resolved with dlsym: libmpmhip.so itself does not link librccl
-  void *h = nullptr;
-  ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;
-  ncclResult_t (*CommInitRank)(ncclComm_t *, int, ncclUniqueId, int) = nullptr;
-  ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-  ncclResult_t (*GroupStart)() = nullptr;
-  ncclResult_t (*GroupEnd)() = nullptr;
-  ncclResult_t (*Send)(const void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-  ncclResult_t (*Recv)(void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-  ncclResult_t (*AllGather)(const void *, void *, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-  ncclResult_t (*AllReduce)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-  const char *(*GetErrorString)(ncclResult_t) = nullptr;
-  ncclComm_t comm = nullptr;
-  int rank = 0, world = 1;
-  bool load(std::string &err) {
-    if (h) return true;
-    // MPMHIP_RCCL_LIB: another library with the same ten entry points (tests/mock_rccl: shared-memory stand-in that lets
-    // 2-3 ranks share the one GPU of a test box, which RCCL itself refuses)
-    const char *over = getenv("MPMHIP_RCCL_LIB");
-    if (over && *over) {
-      h = dlopen(over, RTLD_NOW | RTLD_LOCAL);
-      if (!h) { err = std::string("dlopen MPMHIP_RCCL_LIB=") + over + ": " + dlerror(); return false; }
-      // never silently: the collective library of a production run must be RCCL
-      fprintf(stderr, "[mpmhip] WARNING: MPMHIP_RCCL_LIB is set -- the multi-GPU exchange uses %s INSTEAD OF librccl.so (test hook)\n", over);
-    }
-    if (!h) h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-    if (!h) h = dlopen("/opt/rocm/lib/librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-    if (!h) { err = std::string("dlopen librccl.so.1: ") + dlerror(); return false; }
-    auto sym = [&](const char *n) { void *p = dlsym(h, n); if (!p) err = std::string("dlsym ") + n; return p; };
-    *(void **)&GetUniqueId = sym("ncclGetUniqueId"); *(void **)&CommInitRank = sym("ncclCommInitRank");
-    *(void **)&CommDestroy = sym("ncclCommDestroy"); *(void **)&GroupStart = sym("ncclGroupStart");
-    *(void **)&GroupEnd = sym("ncclGroupEnd"); *(void **)&Send = sym("ncclSend"); *(void **)&Recv = sym("ncclRecv");
-    *(void **)&AllGather = sym("ncclAllGather"); *(void **)&GetErrorString = sym("ncclGetErrorString");
-    *(void **)&AllReduce = sym("ncclAllReduce");
-    return GetUniqueId && CommInitRank && CommDestroy && GroupStart && GroupEnd && Send && Recv && AllGather && AllReduce &&
-           GetErrorString;
-  }
-};
-
-struct RcclPeer {  // one neighbour rank: static ghost lists + per-re-sort shared blocks, all buffers owned here
-  int rank = -1;
-  int *send_p = nullptr, *recv_p = nullptr, *send_e = nullptr, *recv_e = nullptr;
-  int n_send_p = 0, n_recv_p = 0, n_send_e = 0, n_recv_e = 0;
-  float *ghost_send = nullptr, *ghost_recv = nullptr;
-  int *blocks = nullptr, *flag = nullptr, *index = nullptr;
-  int n_blocks = 0, cap_blocks = 0;
-  float *halo_send = nullptr, *halo_recv = nullptr;
-  // peer link: arena = [flag parity 0 | flag parity 1 | data parity 0 | data parity 1], flags 64 B apart, data from word 32,
-  // link_cap blocks x 8 channels x 64 nodes per parity.  link_local is fine-grained memory of this rank that the
-  // neighbour writes; link_remote is the neighbour's arena for this rank (hipIpcOpenMemHandle)
-  float *link_local = nullptr, *link_remote = nullptr;
-  int link_cap = 0;
-  int *link_cnt = nullptr;
-  unsigned char *hbuf = nullptr;  // device staging of the two IPC handles (mine at 0, theirs at 64)
-
-  // what the substep's launches and the exchange use of this peer (FastState::peers), link fields included
-  DistPeer view() const {
-    DistPeer q;
-    q.n_blocks = n_blocks; q.blocks = blocks; q.halo_send = halo_send; q.halo_recv = halo_recv;
-    q.n_send_p = n_send_p; q.n_recv_p = n_recv_p; q.n_send_e = n_send_e; q.n_recv_e = n_recv_e;
-    q.send_p = send_p; q.recv_p = recv_p; q.send_e = send_e; q.recv_e = recv_e;
-    q.ghost_send = ghost_send; q.ghost_recv = ghost_recv;
-    q.link_local = link_local; q.link_remote = link_remote; q.link_cap = link_cap; q.link_cnt = link_cnt;
-    return q;
-  }
-};
-
-// Record sizes of the two exchanges, in floats (mpmavatar_amd/dist.py has the same two functions; include/mpmhip.h states them
-// at mpmhip_dist_peer).  Halo: 64 nodes per channel of a shared block, (m, momentum) = 4 channels, 8 with a particle mover.
-// Ghosts: x, v of a vertex / traditional particle, the director d3 of an element.
-constexpr int HALO_CHANNELS_MAX = 8;  // the in-library loop sizes its halo buffers and link arenas for the wider record
-inline int halo_channels(bool movers) { return movers ? 8 : 4; }
-constexpr size_t halo_floats(size_t n_blocks, int channels) { return n_blocks * (size_t)channels * 64; }
-constexpr size_t ghost_floats(size_t n_p, size_t n_e) { return 6 * n_p + 3 * n_e; }
-// the peer-link arena (layout at RcclPeer): where parity `par`'s data and flag sit
-constexpr int LINK_DATA0 = 32, LINK_FLAG_STRIDE = 16;
-constexpr size_t link_arena_floats(int cap) { return (size_t)LINK_DATA0 + 2 * halo_floats((size_t)cap, HALO_CHANNELS_MAX); }
-inline float *link_data(float *arena, int par, int cap) { return arena + LINK_DATA0 + (size_t)par * halo_floats((size_t)cap, HALO_CHANNELS_MAX); }
-inline int *link_flag(float *arena, int par) { return (int *)arena + par * LINK_FLAG_STRIDE; }
-
 // Pinned host scratch (FastState::h_pin): where the read-backs behind the host's waits land.  One name per slot; a block is
 // [first, first + its _N).  The slots are laid out one after the other, so no two can share a word; the assert keeps that true
 // if one is ever placed by hand.
@@ -186,36 +97,23 @@ class AccumRing {
 };
 
 struct ResortState;
+struct DistState;
 
 struct FastState {
-  Rccl rccl;
-  std::vector<RcclPeer> rpeers;
-  unsigned char *map_all = nullptr;  // [world][nblocks] active-block byte maps
-  bool link_want = true, link_decided = false, link_on = false;  // peer-mapped halos: asked for / decided collectively / in use
-  // fused halo (peer-mapped halos only): pack workgroups ride in the p2g launch, g2p adds the neighbour's share while it
-  // stages its tile (PackArgs, HaloIn) -- no pack / add kernels in the substep.  Decided per collective re-sort (local decision:
-  // what goes over the links is the same either way).  MPMHIP_DIST_FUSED_HALO=0: keep the two kernels.
-  bool fused_want = true, fused_halo = false;
-  int *halo_slot = nullptr, *halo_multi = nullptr;
-  unsigned *pack_done = nullptr, pack_target = 0;
-  int64_t fused_halo_steps = 0;  // substeps that ran without pack / add kernels (mpmhip_dist_fused_halo_steps)
-  unsigned halo_seq = 0;             // substeps exchanged so far (+ handshake rounds): flag value and buffer parity (wraps: the
-                                     // kernels compare (int)(flag - seq), long trainings run billions of substeps)
+  // ---- multi-GPU: the state of the exchange -- communicator, peer list, links, sequence numbers, the collective re-sort's
+  // bookkeeping -- is DistState, defined and owned by dist.hip (dist_alloc / dist_free below).  Four things stay here:
+  DistState *ds = nullptr;
+  bool dist = false;              // the policy switch the substep and the re-sort read: re-sorts only on request (all ranks re-sort
+                                  // together), no kept collider fields, no G2P2G, no split splat
+  bool ghost_g2p = false;         // read by the re-sort (k_keys: which copies go on the g2p list): ghost copies (selection == 2)
+                                  // gather for themselves
+  float global_mass_span = 0.0f;  // read by the re-sort's tile decision: the span over ALL ranks' simulated particles
+                                  // (mpmhip_dist_set_mass_span); 0: not set
+  // (and g.halo below, a device argument: the launcher of g2p picks the kernel by its slot table)
   Dims d{};
-  bool dist = false;  // multi-GPU: re-sorts only on request (all ranks re-sort together)
-  bool dist_keep_cur = false;  // re-sort inside mpmhip_rccl_steps: the caller's mesh pointers are valid
   bool g2p_two_pass = false;   // k_g2p<., true, .>: see there (default: scenes without traditional particles)
   bool p2g_fixed = true;       // p2g's chunk tile in packed fixed point (k_p2g<.., FX = true>); MPMHIP_P2G_TILE=f64: the fp64 tile
   bool p2g_fixed_forced = false;  // ... whatever the mass span (MPMHIP_P2G_TILE=fx)
-  float global_mass_span = 0.0f;  // sharded runs: the span over ALL ranks' simulated particles (mpmhip_dist_set_mass_span); 0: not set
-  // adaptive collective re-sorts (mpmhip_rccl_steps with rebin_interval <= 0): the ranks' drift flags are max-reduced
-  // every DIST_POLL substeps and read DIST_LAG substeps later, so every rank takes the same decision at the same substep
-  int dist_since = 0;
-  bool dist_resort = false, dflag_in_flight = false, rccl_sorted = false;
-  int64_t dflag_check_at = 0;
-  unsigned dflag_seq = 0;  // sequence number of the last reduction posted to host memory (k_post_flag; wraps)
-  std::vector<DistPeer> peers;
-  StepArgs dist_args{};
   int blk_bits = 0, key_bits = 0;  // blk_bits: packed key format kf (field widths) as the kernels take it
   int blk_bits_plain = 0;          // bits of a block id (face-bin sort)
   float lead_steps = 12.0f;        // predictive sort: look this many substeps ahead (half the expected re-sort interval)
@@ -248,7 +146,6 @@ struct FastState {
   // ---- (end of the re-sort's block)
   bool sort_rocprim = false;   // MPMHIP_SORT=rocprim: the library's sort instead (same permutation)
   GridPtrs g{};
-  bool ghost_g2p = false;  // multi-GPU: ghost copies (selection == 2) gather for themselves
   int64_t stat_steps = 0;
   int *h_pin = nullptr;  // pinned host scratch, PIN_N ints (PIN_*)
   bool elem_pending = false;  // element finalise of the last substep still to be done (fused into the next stress)
@@ -316,6 +213,14 @@ void resort_free(FastState *f);                     // (device memory goes with 
 int do_import(mpmhip_ctx *c);
 int rebin(mpmhip_ctx *c);
 int compact_shared_blocks(mpmhip_ctx *c, const int *flag, int n, int *index, int *list, int cap, int *total);
+// dist.hip: all that fast.hip asks of the multi-GPU side
+int dist_alloc(mpmhip_ctx *c);     // DistState and the pack counter (fast_init); reads MPMHIP_DIST_FUSED_HALO and MPMHIP_DIST_HALO
+void dist_free(FastState *f);      // peer links, link arenas, communicator, DistState: BEFORE the sweep of FastState::allocs
+bool dist_fused_halo_now(const mpmhip_ctx *c);  // the fused halo is in force for this substep: no pack / add kernels
+// What of the halo rides in this p2g launch: the pack table and pk.n_wg (0: nothing).  Once the launch is laid out, the second call
+// sets count / done / target and advances the running target by the workgroups that scatter.
+void dist_pack_riders(mpmhip_ctx *c, PackArgs &pk);
+void dist_pack_placed(mpmhip_ctx *c, const LaunchLayout &lay, PackArgs &pk);
 // fast.hip
 int flush_elements(mpmhip_ctx *c);
 int flush_g2p(mpmhip_ctx *c);  // launches the deferred g2p of a G2P2G sequence
