@@ -12,7 +12,7 @@ the optimiser (train_appearance.py:112 and :260-261) and across a densification 
     once each: reset_opacity(_opacity, optimizer)             -> mpmhip_reset_opacity, in front of the first iteration
                densify_and_prune(...) + swap_into(optimizer)  -> mpmhip_densify_plan / _emit, half way
 
-    python examples/appearance_train_demo.py [--steps 30] [--size 64] [--shadow-net]
+    python examples/appearance_train_demo.py [--steps 30] [--size 64] [--shadow-net] [--lpips VGG16.pth LIN.pth]
 
 The scene is the one of appearance_step_demo.py with colours (a 320-face icosphere, two Gaussians per face, degree-1 SH, an 8 x 8
 shadow map standing in for the output of the shadow network); ``cams`` is the affine of the rendered image (train_appearance.py:126),
@@ -24,6 +24,10 @@ of the recovery from it; the demo fails if the last loss is not below the first.
 ``AOBaker.bake(verts)`` -> ``ShadowUNet(ao_map)["shadow_map"]`` -> ``shaded_colors``, with ``shadow_net.parameters()`` as the
 ``shadow`` group.  The sphere's UVs are its vertex directions (front and back share texels; the baker keeps one face per texel),
 the AO map is 32 x 32, the network works at 16 x 16 with four channels and hands the 8 x 8 map on.
+
+``--lpips VGG16.pth LIN.pth`` adds the third term of train_appearance.py:133-134, ``lambda_lpips * lpips_net(image[None], gt[None])``
+with the reference's lambda_lpips = 0.1, from mpmavatar_amd/lpips.py over the caller's two weight files (torchvision's VGG16 state dict
+and the upstream vgg.pth).  Off by default: the weights are not shipped.
 """
 import argparse
 import os
@@ -39,12 +43,14 @@ from appearance_step_demo import MAP_SIZE, SH_DEGREE, Scene  # noqa: E402
 from mpmavatar_amd.ao_bake import AOBaker  # noqa: E402
 from mpmavatar_amd.densify import DensifyStats, adam_moments, densify_and_prune, reset_opacity  # noqa: E402
 from mpmavatar_amd.image_loss import image_loss  # noqa: E402
+from mpmavatar_amd.lpips import LPIPS  # noqa: E402
 from mpmavatar_amd.optim import FusedAdam, appearance_param_groups, update_learning_rate  # noqa: E402
 from mpmavatar_amd.rasterizer import GaussianRasterizer  # noqa: E402
 from mpmavatar_amd.render_inputs import BoundGaussians  # noqa: E402
 from mpmavatar_amd.shadow_net import ShadowUNet  # noqa: E402
 
 EXTENT = 1.0
+LAMBDA_LPIPS = 0.1                      # arguments/__init__.py
 AO_SIZE = 32
 # the names of arguments/__init__.py:115-126 with rates for this scene
 OPT = SimpleNamespace(position_lr_init=5e-3, position_lr_final=5e-4, position_lr_delay_mult=0.01, position_lr_max_steps=30,
@@ -56,9 +62,10 @@ class TrainScene(Scene):
     """the scene of appearance_step_demo.py --colors whose render keeps ``means2D`` as a leaf and whose image passes the camera's
     affine"""
 
-    def __init__(self, size, shadow_net=False):
+    def __init__(self, size, shadow_net=False, lpips=None):
         super().__init__(size, colors=True)
         dev = self.verts_orig.device
+        self.lpips_net = LPIPS.from_checkpoints(*lpips).to(dev) if lpips else None
         self.cam_m, self.cam_c = torch.nn.Parameter(torch.ones(3, device=dev)), torch.nn.Parameter(torch.zeros(3, device=dev))
         self.baker = self.shadow_net = None
         if shadow_net:
@@ -83,7 +90,11 @@ class TrainScene(Scene):
     def loss(self):
         image, radii = self.render()
         image = image * self.cam_m[:, None, None] + self.cam_c[:, None, None]
-        return image_loss(image.contiguous(), self.target, 0.2)[0], radii
+        image = image.contiguous()
+        loss = image_loss(image, self.target, 0.2)[0]
+        if self.lpips_net is not None:  # train_appearance.py:133-134
+            loss = loss + LAMBDA_LPIPS * self.lpips_net(image.unsqueeze(0), self.target.unsqueeze(0)).reshape(())
+        return loss, radii
 
 
 def main(argv=None):
@@ -91,8 +102,10 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--size", type=int, default=64)
     ap.add_argument("--shadow-net", action="store_true", help="train a ShadowUNet behind AOBaker in place of the bare shadow map")
+    ap.add_argument("--lpips", nargs=2, metavar=("VGG16.pth", "LIN.pth"), default=None,
+                    help="add lambda_lpips * LPIPS from these two weight files (torchvision's VGG16 state dict, the upstream vgg.pth)")
     a = ap.parse_args(argv)
-    sc = TrainScene(a.size, a.shadow_net)
+    sc = TrainScene(a.size, a.shadow_net, a.lpips)
     p = sc.params
     shadow = list(sc.shadow_net.parameters()) if a.shadow_net else [p["shadow_map"]]
     groups = appearance_param_groups(p["_xyz"], p["_features_dc"], p["_features_rest"], p["_opacity"], p["_scaling"], p["_rotation"],

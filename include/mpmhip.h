@@ -425,6 +425,43 @@ int mpmhip_shadow_forward(int32_t device, void *stream, const mpmhip_shadow_desc
 int mpmhip_shadow_backward(int32_t device, void *stream, const mpmhip_shadow_desc *desc, const float *ao_map, const float *lowres,
                            const float *g_shadow_map, const float *g_lowres, void *workspace, int64_t workspace_bytes);
 
+/* ---- LPIPS, the third term of the image loss (lpipsPyTorch/modules/{lpips,networks,utils}.py, net_type 'vgg', version 0.1; called at
+ * train_appearance.py:133 and :231, eval.py:59) ---------------------------------------------------------------------------------------
+ * x, y [n, 3, h, w] -> out [1]: z-score with mean / std, torchvision's vgg16().features[0:30] (thirteen conv3x3 + bias + ReLU with
+ * channels 3-64, 64 | 128, 128 | 256 x3 | 512 x3 | 512 x3, MaxPool2d(2, 2) at the bars), at each of the five taps the channel-normalised
+ * squared difference weighted by tap_weight [C] and averaged over the pixels, summed over the taps AND over the n images (the
+ * reference's sum over the batch it concatenated).  weight [L]: [cout, cin, 3, 3]; bias [L]: [cout]; weight_bwd [L]: cout*cin*9 floats
+ * that mpmhip_lpips_prepare_weights fills ([cin, cout, 3, 3], flipped), read by the backward pass alone.  fp32 on the f32-input MFMA,
+ * every sum in a fixed order, no floating-point atomics: the same input gives the same bits. */
+#define MPMHIP_LPIPS_LAYERS 13
+#define MPMHIP_LPIPS_TAPS 5
+typedef struct {
+  int32_t n, h, w;
+  int32_t reserved_;
+  const float *weight[MPMHIP_LPIPS_LAYERS];
+  const float *bias[MPMHIP_LPIPS_LAYERS];
+  float *weight_bwd[MPMHIP_LPIPS_LAYERS];
+  const float *tap_weight[MPMHIP_LPIPS_TAPS];
+  float mean[3], std[3];
+} mpmhip_lpips_desc;
+/* One launch that fills every weight_bwd [L] from weight [L]; to be repeated when a weight changes.  Sizes are not read. */
+int mpmhip_lpips_prepare_weights(int32_t device, void *stream, const mpmhip_lpips_desc *desc);
+/* The workspace for desc's n, h, w (its pointers are not read).  keep = 1: a forward pass whose backward pass will follow (the
+ * thirteen maps of x, the five tap maps of y, the tap gradients and two gradient buffers); keep = 0: a forward pass alone (the taps and
+ * two alternating buffers per image).  Host arithmetic: written whenever the arguments are valid, and the return is then that of the
+ * device check.  MPMHIP_ERR_INVALID: n < 0 or > 1024, h or w < 16 (four poolings must leave 1 x 1) or > 8192, keep not 0 or 1. */
+int mpmhip_lpips_workspace_bytes(int32_t device, void *stream, const mpmhip_lpips_desc *desc, int32_t keep, int64_t *out_workspace_bytes);
+/* out [1].  19 launches.  keep as above; weight_bwd may be NULL with keep = 0.  MPMHIP_ERR_INVALID also: a NULL weight, bias, input or
+ * output, a zero or non-finite std, a workspace that is too small.  n == 0: out = 0. */
+int mpmhip_lpips_forward(int32_t device, void *stream, const mpmhip_lpips_desc *desc, const float *x, const float *y, int32_t keep,
+                         void *workspace, int64_t workspace_bytes, float *out);
+/* dx [n, 3, h, w] = g_out [1] * d out / d x over the workspace a forward pass with keep = 1 left (same desc, x and y no longer needed).
+ * 18 launches.  ReLU's derivative is read off the saved output (> 0); a pooling window's gradient goes to its first maximum in
+ * row-major order; a tap pixel whose feature vector is all zero contributes nothing (the reference yields NaN there).  There is no
+ * gradient to y or to a weight: the network is frozen. */
+int mpmhip_lpips_backward(int32_t device, void *stream, const mpmhip_lpips_desc *desc, const float *g_out, void *workspace,
+                          int64_t workspace_bytes, float *dx);
+
 /* ---- the regularisation terms of the appearance loop (train_appearance.py:136-150) ------------------------------------------------
  * What the reference computes between render(...) and loss.backward() besides the image loss, as two fused ops with exact backward
  * passes.  Stand-alone maps on [dev] arrays; nothing allocates or synchronises; fp32 data, sums in fp64 in a fixed order, no

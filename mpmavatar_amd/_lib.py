@@ -80,6 +80,11 @@ class ShadowDesc(C.Structure):
                 ("d_weight_v", vp * 9), ("d_weight_g", vp * 9), ("d_bias", vp * 9)]
 
 
+class LpipsDesc(C.Structure):
+    _fields_ = [("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("reserved_", C.c_int32), ("weight", vp * 13), ("bias", vp * 13),
+                ("weight_bwd", vp * 13), ("tap_weight", vp * 5), ("mean", f3), ("std", f3)]
+
+
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
 SIGNATURES = {
     "mpmhip_version": (C.c_int, []),
@@ -117,6 +122,10 @@ SIGNATURES = {
     "mpmhip_shadow_workspace_bytes": (C.c_int, [C.c_int32, vp, C.POINTER(ShadowDesc), C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
     "mpmhip_shadow_forward": (C.c_int, [C.c_int32, vp, C.POINTER(ShadowDesc), vp, vp, C.c_int64, vp, vp, vp]),
     "mpmhip_shadow_backward": (C.c_int, [C.c_int32, vp, C.POINTER(ShadowDesc), vp, vp, vp, vp, vp, C.c_int64]),
+    "mpmhip_lpips_prepare_weights": (C.c_int, [C.c_int32, vp, C.POINTER(LpipsDesc)]),
+    "mpmhip_lpips_workspace_bytes": (C.c_int, [C.c_int32, vp, C.POINTER(LpipsDesc), C.c_int32, C.POINTER(C.c_int64)]),
+    "mpmhip_lpips_forward": (C.c_int, [C.c_int32, vp, C.POINTER(LpipsDesc), vp, vp, C.c_int32, vp, C.c_int64, vp]),
+    "mpmhip_lpips_backward": (C.c_int, [C.c_int32, vp, C.POINTER(LpipsDesc), vp, vp, C.c_int64, vp]),
     "mpmhip_mesh_reg_forward": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32] + [vp] * 7),
     "mpmhip_mesh_reg_backward": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32] + [vp] * 9),
     "mpmhip_gauss_reg_forward": (C.c_int, [C.c_int32, vp, C.c_int32] + [vp] * 5 + [C.c_float, C.c_float] + [vp] * 3),

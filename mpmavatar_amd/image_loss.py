@@ -19,8 +19,9 @@ backward launch (the two separate calls above cost two of each and give the same
         ev.add_frame(img_pred, img_gt, mask)                   # nothing leaves the device, nothing synchronises
     ev.save(output_path)                                       # app_metric.npz, keys "PSNR" and "SSIM"
 
-LPIPS (train_appearance.py:133, eval.py:89) is NOT here: it needs the VGG and LPIPS weights, which this project does not
-ship; the caller keeps its own ``lpips`` module and adds that term itself, and ``app_metric.npz`` has no "LPIPS" key.
+LPIPS (train_appearance.py:133, eval.py:89) is ``mpmavatar_amd/lpips.py`` (its weights are the caller's files): the caller adds
+``lambda_lpips * lpips_net(image[None], gt[None])`` to ``image_loss``'s result, and ``AppEval(lpips=lpips_net)`` adds the "LPIPS" key
+of ``app_metric.npz``.
 
 All four functions share one ``torch.autograd.Function`` whose outputs are the per-plane means (a plane is one (batch,
 channel) image) of |d|, d^2 and the SSIM map as three ``[planes]`` tensors; the means over planes, ``1 - ssim``, the lambda
@@ -146,15 +147,17 @@ def image_loss(image, gt, lambda_dssim=0.2):
 
 class AppEval:
     """The appearance loop of eval.py:59-98 with the metrics on the device: one (PSNR, SSIM) pair per frame, kept as device
-    scalars.  The mask erosion and white-pixel removal of eval.py:71-83 stay the caller's (OpenCV and torch); LPIPS is not
-    computed and app_metric.npz has no "LPIPS" key."""
+    scalars.  The mask erosion and white-pixel removal of eval.py:71-83 stay the caller's (OpenCV and torch).  With
+    ``lpips`` (a module of mpmavatar_amd/lpips.py with its weights loaded) every frame also gets the LPIPS of the masked pair
+    (eval.py:89) and app_metric.npz its "LPIPS" key; without it LPIPS is not computed and the file has no such key."""
 
-    def __init__(self):
-        self.psnrs, self.ssims = [], []
+    def __init__(self, lpips=None):
+        self.psnrs, self.ssims, self.lpips, self.lpipss = [], [], lpips, []
 
     def add_frame(self, img_pred, img_gt, mask=None):
         """eval.py:86-91: both images times the mask if given, a [C, H, W] image made a batch of one as there (so that the
-        PSNR is that of the whole image, not the mean over its channels), then psnr(...) and ssim(...).  Returns the pair."""
+        PSNR is that of the whole image, not the mean over its channels), then psnr(...) and ssim(...).  Returns the pair
+        (PSNR, SSIM), or the triple (PSNR, SSIM, LPIPS) where the evaluation has an LPIPS module."""
         with torch.no_grad():
             if mask is not None:
                 img_pred, img_gt = img_pred * mask, img_gt * mask
@@ -162,17 +165,23 @@ class AppEval:
                 img_pred, img_gt = img_pred.unsqueeze(0), img_gt.unsqueeze(0)
             _, mse, m = plane_means(img_pred, img_gt)
             pair = _psnr_from(mse, img_pred.dim()).mean(), m.mean()
+            if self.lpips is not None:
+                pair = pair + (self.lpips(img_pred, img_gt).reshape(()),)
         self.psnrs.append(pair[0])
         self.ssims.append(pair[1])
+        if self.lpips is not None:
+            self.lpipss.append(pair[2])
         return pair
 
     def results(self):
         """{"PSNR": [...], "SSIM": [...]} per frame on the host (the one synchronisation): the fp32 device values as float64,
-        what the reference's lists of .item() become in np.savez."""
+        what the reference's lists of .item() become in np.savez; with an LPIPS module also "LPIPS", first as in eval.py:59."""
+        rows = ([self.lpipss] if self.lpips is not None else []) + [self.psnrs, self.ssims]
+        keys = (["LPIPS"] if self.lpips is not None else []) + ["PSNR", "SSIM"]
         if not self.psnrs:
-            return {"PSNR": np.zeros(0, np.float64), "SSIM": np.zeros(0, np.float64)}
-        r = torch.stack([torch.stack(self.psnrs), torch.stack(self.ssims)]).cpu().numpy().astype(np.float64)
-        return {"PSNR": r[0].copy(), "SSIM": r[1].copy()}
+            return {k: np.zeros(0, np.float64) for k in keys}
+        r = torch.stack([torch.stack(row) for row in rows]).cpu().numpy().astype(np.float64)
+        return {k: r[i].copy() for i, k in enumerate(keys)}
 
     def means(self):
         """(mean PSNR, mean SSIM) over the frames, as eval.py:93-95 prints them."""
@@ -180,9 +189,9 @@ class AppEval:
         return float(r["PSNR"].mean()), float(r["SSIM"].mean())
 
     def save(self, directory):
-        """app_metric.npz as eval.py:98 writes it, without its "LPIPS" key; plain arrays, loads without pickle."""
+        """app_metric.npz as eval.py:98 writes it ("LPIPS" only with an LPIPS module); plain arrays, loads without pickle."""
         r = self.results()
         os.makedirs(directory, exist_ok=True)
         path = os.path.join(directory, "app_metric.npz")
-        np.savez(path, PSNR=r["PSNR"], SSIM=r["SSIM"])
+        np.savez(path, **r)
         return path
