@@ -12,7 +12,7 @@ the optimiser (train_appearance.py:112 and :260-261) and across a densification 
     once each: reset_opacity(_opacity, optimizer)             -> mpmhip_reset_opacity, in front of the first iteration
                densify_and_prune(...) + swap_into(optimizer)  -> mpmhip_densify_plan / _emit, half way
 
-    python examples/appearance_train_demo.py [--steps 30] [--size 64] [--shadow-net] [--lpips VGG16.pth LIN.pth]
+    python examples/appearance_train_demo.py [--steps 30] [--size 64] [--shadow-net] [--lpips VGG16.pth LIN.pth] [--image-head]
 
 The scene is the one of appearance_step_demo.py with colours (a 320-face icosphere, two Gaussians per face, degree-1 SH, an 8 x 8
 shadow map standing in for the output of the shadow network); ``cams`` is the affine of the rendered image (train_appearance.py:126),
@@ -28,6 +28,11 @@ the AO map is 32 x 32, the network works at 16 x 16 with four channels and hands
 ``--lpips VGG16.pth LIN.pth`` adds the third term of train_appearance.py:133-134, ``lambda_lpips * lpips_net(image[None], gt[None])``
 with the reference's lambda_lpips = 0.1, from mpmavatar_amd/lpips.py over the caller's two weight files (torchvision's VGG16 state dict
 and the upstream vgg.pth).  Off by default: the weights are not shipped.
+
+``--image-head`` puts the reference's own two lines between the render call and the loss (train_appearance.py:126-127) in place of
+the bare affine: ``camera_image(image, alpha, cam_m, cam_c, None)`` of mpmavatar_amd/image_head.py -- the gain is ``exp(cam_m)`` with
+``cam_m`` starting at zero, the image is multiplied by the rasteriser's alpha and clipped to [0, 1], in one launch forward and two
+backward.  Without the flag the example runs as it always did.
 """
 import argparse
 import os
@@ -42,6 +47,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from appearance_step_demo import MAP_SIZE, SH_DEGREE, Scene  # noqa: E402
 from mpmavatar_amd.ao_bake import AOBaker  # noqa: E402
 from mpmavatar_amd.densify import DensifyStats, adam_moments, densify_and_prune, reset_opacity  # noqa: E402
+from mpmavatar_amd.image_head import camera_image, compose_gt  # noqa: E402
 from mpmavatar_amd.image_loss import image_loss  # noqa: E402
 from mpmavatar_amd.lpips import LPIPS  # noqa: E402
 from mpmavatar_amd.optim import FusedAdam, appearance_param_groups, update_learning_rate  # noqa: E402
@@ -62,11 +68,15 @@ class TrainScene(Scene):
     """the scene of appearance_step_demo.py --colors whose render keeps ``means2D`` as a leaf and whose image passes the camera's
     affine"""
 
-    def __init__(self, size, shadow_net=False, lpips=None):
+    def __init__(self, size, shadow_net=False, lpips=None, image_head=False):
         super().__init__(size, colors=True)
         dev = self.verts_orig.device
         self.lpips_net = LPIPS.from_checkpoints(*lpips).to(dev) if lpips else None
-        self.cam_m, self.cam_c = torch.nn.Parameter(torch.ones(3, device=dev)), torch.nn.Parameter(torch.zeros(3, device=dev))
+        self.image_head = image_head                     # cam_m is then the logarithm of the gain: it starts at zero
+        self.cam_m = torch.nn.Parameter(torch.zeros(3, device=dev) if image_head else torch.ones(3, device=dev))
+        self.cam_c = torch.nn.Parameter(torch.zeros(3, device=dev))
+        if image_head:                  # train_appearance.py:108: the ground truth is composed with ITS mask, the target render's alpha
+            self.target = compose_gt(self.target, self.alpha)
         self.baker = self.shadow_net = None
         if shadow_net:
             direction = self.verts_orig / self.verts_orig.norm(dim=1, keepdim=True)
@@ -84,13 +94,16 @@ class TrainScene(Scene):
         args = self.gaussians.render_inputs(self.frames, override_color=self.colors)
         args["colors_precomp"] = self.gaussians.shaded_colors(args["means3D"], self.campos, SH_DEGREE, shadow_map=self.shadow_map, sampler=self.sampler)
         self.means2D = args["means2D"].requires_grad_(torch.is_grad_enabled())
-        image, _, _, _, radii, _ = GaussianRasterizer(raster_settings=self.settings)(**args)
+        image, _, _, self.alpha, radii, _ = GaussianRasterizer(raster_settings=self.settings)(**args)
         return image, radii
 
     def loss(self):
         image, radii = self.render()
-        image = image * self.cam_m[:, None, None] + self.cam_c[:, None, None]
-        image = image.contiguous()
+        if self.image_head:             # train_appearance.py:126-127
+            image = camera_image(image, self.alpha, self.cam_m, self.cam_c, None)
+        else:
+            image = image * self.cam_m[:, None, None] + self.cam_c[:, None, None]
+            image = image.contiguous()
         loss = image_loss(image, self.target, 0.2)[0]
         if self.lpips_net is not None:  # train_appearance.py:133-134
             loss = loss + LAMBDA_LPIPS * self.lpips_net(image.unsqueeze(0), self.target.unsqueeze(0)).reshape(())
@@ -104,8 +117,12 @@ def main(argv=None):
     ap.add_argument("--shadow-net", action="store_true", help="train a ShadowUNet behind AOBaker in place of the bare shadow map")
     ap.add_argument("--lpips", nargs=2, metavar=("VGG16.pth", "LIN.pth"), default=None,
                     help="add lambda_lpips * LPIPS from these two weight files (torchvision's VGG16 state dict, the upstream vgg.pth)")
+    ap.add_argument("--image-head", action="store_true",
+                    help="the reference's affine, mask and clip between the render call and the loss: mpmavatar_amd.image_head.camera_image")
     a = ap.parse_args(argv)
-    sc = TrainScene(a.size, a.shadow_net, a.lpips)
+    sc = TrainScene(a.size, a.shadow_net, a.lpips, a.image_head)
+    if a.image_head:
+        print("image head: camera_image(image, alpha, cam_m, cam_c, None) between the render call and the loss")
     p = sc.params
     shadow = list(sc.shadow_net.parameters()) if a.shadow_net else [p["shadow_map"]]
     groups = appearance_param_groups(p["_xyz"], p["_features_dc"], p["_features_rest"], p["_opacity"], p["_scaling"], p["_rotation"],

@@ -787,6 +787,62 @@ int mpmhip_image_loss_forward(int32_t device, void *stream, const float *img, co
 int mpmhip_image_loss_backward(int32_t device, void *stream, const float *img, const float *gt, int32_t planes, int32_t H, int32_t W,
                                const float *maps, const float *g_l1, const float *g_mse, const float *g_ssim, float *d_img);
 
+/* ---- between the rasteriser and the loss: the image head -------------------------------------------------------------------
+ * The expression between the render call and the loss of train_appearance.py:126-127 (again at :206-207 and in
+ * train_material_params.py:865-870),
+ *   image = render * exp(cam_m[camera_idx])[:, None, None] + cam_c[camera_idx][:, None, None]
+ *   image = (image * mask).clip(0., 1.)
+ * with its gradient, and the forward-only maps of the evaluation side.  Stand-alone maps on [dev] arrays (no context; `stream`
+ * is a hipStream_t, NULL = default stream); nothing here allocates or synchronises, every buffer is the caller's.  render
+ * [3*H*W] (CHW), mask [H*W] (the rasteriser's alpha), cam_m and cam_c [n_cam*3]; `cam` is the camera's row, read on the device.
+ * All return MPMHIP_ERR_INVALID, with nothing launched, for a NULL required pointer, H or W <= 0, H * W > 2^31 - 1, n_cam <= 0
+ * or cam outside [0, n_cam).  All arithmetic fp32 with every operation rounded on its own as torch rounds them, no
+ * floating-point atomics: the same input gives the same bits.  A lane takes four consecutive pixels; planes that are 16-byte
+ * aligned with H * W % 4 == 0 are read and written 16 bytes at a time, anything else pixel by pixel, with the same results.
+ *
+ * mpmhip_image_head_forward: out_image [3*H*W], v = (render[c] * exp(cam_m[cam][c]) + cam_c[cam][c]) * mask,
+ * image = min(max(v, 0), 1), NaN propagating as in torch.  One launch.
+ *
+ * Workgroups of the forward and backward launches and doubles of the backward scratch, pure functions of H * W: one
+ * workgroup of 256 lanes per 1024 pixels, at most 1024 (beyond 1024 x 1024 pixels they stride over the image), six sums each. */
+#define MPMHIP_IMAGE_HEAD_WORKGROUPS(H, W) \
+  ((((int64_t)(H) * (W) + 1023) / 1024) < 1024 ? (((int64_t)(H) * (W) + 1023) / 1024) : (int64_t)1024)
+#define MPMHIP_IMAGE_HEAD_SCRATCH(H, W) (MPMHIP_IMAGE_HEAD_WORKGROUPS(H, W) * 6)
+int mpmhip_image_head_forward(int32_t device, void *stream, const float *render, const float *mask, const float *cam_m, const float *cam_c,
+                              int32_t n_cam, int32_t cam, int32_t H, int32_t W, float *out_image);
+/* What autograd does for loss.backward() through those two lines (train_appearance.py:155): from g_image [3*H*W] (NULL counts
+ * as zeros) to the four gradients, each wanted on its own (NULL = not wanted; every wanted output is written in full).  The
+ * clip has TORCH's slope: with v recomputed by the forward's own function, g_v = g_image where 0 <= v <= 1, both ends
+ * included, and 0 elsewhere -- a pixel with mask == 0 has v == 0 exactly and still hands a gradient to mask.  a_c =
+ * exp(cam_m[cam][c]):
+ *   d_render [3*H*W]    g_v * mask * a_c
+ *   d_mask [H*W]        sum_c g_v[c] * (render[c] * a_c + cam_c[cam][c])
+ *   d_cam_c [n_cam*3]   row cam: sum_pixels g_v[c] * mask; every other row zero
+ *   d_cam_m [n_cam*3]   row cam: a_c * sum_pixels g_v[c] * mask * render[c]; every other row zero
+ * the dense tensors torch's index backward hands to the optimiser.  The pixel sums have fp32 terms and fp64 additions in an
+ * order that depends on H * W alone: per-workgroup partials in scratch [MPMHIP_IMAGE_HEAD_SCRATCH(H, W)] doubles (required
+ * when d_cam_m or d_cam_c is wanted), folded in index order by one workgroup that also writes both [n_cam*3] outputs.  Two
+ * launches, one when neither d_cam_m nor d_cam_c is wanted, none when nothing is. */
+int mpmhip_image_head_backward(int32_t device, void *stream, const float *render, const float *mask, const float *cam_m, const float *cam_c,
+                               int32_t n_cam, int32_t cam, int32_t H, int32_t W, const float *g_image, double *scratch, float *d_render,
+                               float *d_mask, float *d_cam_m, float *d_cam_c);
+/* The evaluation side, forward only: what replaces the PNG, OpenCV and host detour of train_material_params.py:865-876 and
+ * eval.py:68-87.  One launch each.
+ * mpmhip_image_head_bytes (train_material_params.py:865-870): r = (render * exp(cam_m[cam]) + cam_c[cam]) * mask, plus
+ * (1 - mask) if white != 0, then (clamp(r, 0, 1) * 255.f) truncated toward zero, stored HWC in out_u8 [H*W*3].  cam_m and
+ * cam_c both NULL: the identity (n_cam and cam are not looked at), which makes the ground-truth frame of :847-849 and :874
+ * from (gt_rgb, gt_msk); one of them NULL alone is MPMHIP_ERR_INVALID.
+ * mpmhip_image_compose (train_appearance.py:108-110): out [3*H*W] = rgb * msk, plus (1 - msk) if white != 0; not clipped.
+ * mpmhip_eval_pair (eval.py:68-87): from the two byte frames pred_u8, gt_u8 [H*W*3] (HWC) and the float mask [H*W] to
+ * out_pred, out_gt [3*H*W] (CHW): byte / 255 as a true fp32 division; with remove_white != 0 (the actorshq branch, :73-76) a
+ * pixel whose three bytes sum to >= 689 -- for bytes exactly mean(axis=0) > 0.90 -- is zero in that image, each image on its
+ * own; then both times the mask. */
+int mpmhip_image_head_bytes(int32_t device, void *stream, const float *render, const float *mask, const float *cam_m, const float *cam_c,
+                            int32_t n_cam, int32_t cam, int32_t white, int32_t H, int32_t W, uint8_t *out_u8);
+int mpmhip_image_compose(int32_t device, void *stream, const float *rgb, const float *msk, int32_t white, int32_t H, int32_t W, float *out);
+int mpmhip_eval_pair(int32_t device, void *stream, const uint8_t *pred_u8, const uint8_t *gt_u8, const float *mask, int32_t remove_white,
+                     int32_t H, int32_t W, float *out_pred, float *out_gt);
+
 /* ---- introspection ---------------------------------------------------------------------- */
 /* dense reference-layout copies of grid_m [G^3], grid_v_in [G^3*3], grid_v_out [G^3*3] as they
  * stand after the last substep's grid stage ([dev] outputs, any may be NULL).  Synchronous. */

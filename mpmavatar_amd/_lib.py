@@ -158,6 +158,11 @@ SIGNATURES = {
     "mpmhip_raster_profile": (C.c_int, [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "mpmhip_image_loss_forward": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]),
     "mpmhip_image_loss_backward": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]),
+    "mpmhip_image_head_forward": (C.c_int, [C.c_int32, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]),
+    "mpmhip_image_head_backward": (C.c_int, [C.c_int32, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [vp] * 6),
+    "mpmhip_image_head_bytes": (C.c_int, [C.c_int32, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]),
+    "mpmhip_image_compose": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp]),
+    "mpmhip_eval_pair": (C.c_int, [C.c_int32, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
     "mpmhip_dist_enable": (C.c_int, [vp]),
     "mpmhip_dist_set_ghost_mode": (C.c_int, [vp, C.c_int32]),
     "mpmhip_dist_set_mass_span": (C.c_int, [vp, C.c_float, C.c_float]),

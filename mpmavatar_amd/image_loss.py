@@ -147,7 +147,8 @@ def image_loss(image, gt, lambda_dssim=0.2):
 
 class AppEval:
     """The appearance loop of eval.py:59-98 with the metrics on the device: one (PSNR, SSIM) pair per frame, kept as device
-    scalars.  The mask erosion and white-pixel removal of eval.py:71-83 stay the caller's (OpenCV and torch).  With
+    scalars.  The mask erosion and white-pixel removal of eval.py:71-83 are ``eval_mask`` and ``eval_inputs`` of
+    mpmavatar_amd/image_head.py, whose pair goes straight into ``add_frame``.  With
     ``lpips`` (a module of mpmavatar_amd/lpips.py with its weights loaded) every frame also gets the LPIPS of the masked pair
     (eval.py:89) and app_metric.npz its "LPIPS" key; without it LPIPS is not computed and the file has no such key."""
 
