@@ -843,6 +843,76 @@ int mpmhip_image_compose(int32_t device, void *stream, const float *rgb, const f
 int mpmhip_eval_pair(int32_t device, void *stream, const uint8_t *pred_u8, const uint8_t *gt_u8, const float *mask, int32_t remove_white,
                      int32_t H, int32_t W, float *out_pred, float *out_gt);
 
+/* ---- the mesh tracking step (preprocess/train_mesh_lbs_actorshq.py:209-279) ---------------------------------------------------------
+ * What the tracking loop computes between the trained vertices and the rasteriser's argument list, and the loss terms the
+ * appearance loop does not have.  Stand-alone maps on [dev] arrays; nothing allocates or synchronises; fp32 data, sums in fp64 in a
+ * fixed order, no floating-point atomics: the same input gives the same bits.  faces [n_faces*3] index verts [n_verts*3]; an index
+ * outside [0, n_verts) reads nothing and gives NaN.  A zero-area face gives NaN, as in the reference.  MPMHIP_ERR_INVALID, nothing
+ * launched: a negative count, 3 * n_faces > 2^31 - 1, a required pointer NULL.  n_faces == 0: MPMHIP_OK.
+ *
+ * mpmhip_track_render_vars (params2rendervar :209-225), one Gaussian per face, one launch:
+ *   out_means3D [n_faces*3]  (v1 + v2 + v3) / 3                                  compute_face_barycenters (utils/geo_utils.py:32-38)
+ *   out_rotations [n_faces*4] WXYZ, the quaternion of the matrix with columns x, y, z: x the longest of e1 = v2 - v1, e2 = v3 - v2,
+ *                 e3 = v1 - v3 (the first of the longest), normalised; z the normal of compute_face_normals (:21-30) normalised
+ *                 again; y = z x x, normalised                                   compute_q_from_faces (:40-75)
+ *   out_scales [n_faces*3] exp(log_scales);  out_opacities [n_faces] sigmoid(logit_opacities)
+ * The matrix -> quaternion map restates pytorch3d.transforms.matrix_to_quaternion (roots sqrt(max(0, 1 +- m00 +- m11 +- m22)), rows
+ * divided by 2 max(root, 0.1), the row of the largest root, then w >= 0) and is UNCONFIRMED against pytorch3d itself; q and -q are
+ * the same rotation. */
+#define MPMHIP_TRACK_TPB 256
+int mpmhip_track_render_vars(int32_t device, void *stream, const float *verts, int32_t n_verts, const int32_t *faces, int32_t n_faces,
+                             const float *log_scales, const float *logit_opacities, float *out_means3D, float *out_rotations,
+                             float *out_scales, float *out_opacities);
+/* mpmhip_track_render_vars_backward: from the four upstream gradients (each may be NULL = zeros) to d_verts [n_verts*3],
+ * d_log_scales [n_faces*3], d_logit_opacities [n_faces], each written in full, NULL = not wanted.  The exact derivative with the
+ * longest edge and the quaternion's branch and sign held fixed.  d_stencil [n_faces*9] is scratch for the gradient of each corner;
+ * vert_start [n_verts+1] / vert_items [3*n_faces] is the vertex -> corner table (item = 3 f + c, ascending within a vertex), which a
+ * vertex walks serially: a vertex in no face gets exactly 0.  The table and d_stencil are needed only with d_verts. */
+int mpmhip_track_render_vars_backward(int32_t device, void *stream, const float *verts, int32_t n_verts, const int32_t *faces, int32_t n_faces,
+                                      const float *log_scales, const float *logit_opacities, const float *g_means3D, const float *g_rotations,
+                                      const float *g_scales, const float *g_opacities, const int32_t *vert_start, const int32_t *vert_items,
+                                      float *d_stencil, float *d_verts, float *d_log_scales, float *d_logit_opacities);
+/* compute_face_normals and compute_face_areas (utils/geo_utils.py:21-30, :77-85): out_normals [n_faces*3], out_areas [n_faces], either
+ * may be NULL.  Forward only. */
+int mpmhip_track_face_geometry(int32_t device, void *stream, const float *verts, int32_t n_verts, const int32_t *faces, int32_t n_faces,
+                               float *out_normals, float *out_areas);
+/* The loss terms of :242, :254, :263-268:
+ *   out_terms[0] area    = mean_f | |e1 x e2| / 2 - pi s0 s1 |,  s = exp(log_scales)
+ *   out_terms[1] scale   = mean_f s2
+ *   out_terms[2] opacity = mean_f (1 - sigmoid(logit_opacities))
+ * scratch [MPMHIP_TRACK_TERMS_SCRATCH(n_faces)] doubles.  n_faces == 0: nothing written. */
+#define MPMHIP_TRACK_TERMS_SCRATCH(n_faces) (3 * (((int64_t)(n_faces) + MPMHIP_TRACK_TPB - 1) / MPMHIP_TRACK_TPB))
+int mpmhip_track_terms_forward(int32_t device, void *stream, const float *verts, int32_t n_verts, const int32_t *faces, int32_t n_faces,
+                               const float *log_scales, const float *logit_opacities, double *scratch, float *out_terms);
+/* from g_terms [3] on the device to d_verts, d_log_scales, d_logit_opacities as above; sign(0) = 0 inside the absolute value */
+int mpmhip_track_terms_backward(int32_t device, void *stream, const float *verts, int32_t n_verts, const int32_t *faces, int32_t n_faces,
+                                const float *log_scales, const float *logit_opacities, const float *g_terms, const int32_t *vert_start,
+                                const int32_t *vert_items, float *d_stencil, float *d_verts, float *d_log_scales, float *d_logit_opacities);
+/* compute_vertex_normals (utils/geo_utils.py:8-19): out_normals [n_verts*3] = the sum over the vertex's faces, in ascending face order
+ * through the table above, of (v0 - v1) x (v2 - v1), normalised.  A vertex in no face gives NaN (0 / 0), as in the reference.
+ * Forward only. */
+int mpmhip_track_vertex_normals(int32_t device, void *stream, const float *verts, int32_t n_verts, const int32_t *faces, int32_t n_faces,
+                                const int32_t *vert_start, const int32_t *vert_items, float *out_normals);
+/* collision_penalty (preprocess/losses/physics.py:6-20) without the [n, n_body] distance matrix: out_index [n] = the nearest of
+ * vb [n_body*3] to va[i] by the kernel of mpmhip_nn_dist2 (the exact minimum of the direct-form squared distance, the lowest index on
+ * a tie); with nb [n_body*3] given, out_distance [n] = -nb[j] . (va[i] - vb[j]) and, by mode,
+ *   MPMHIP_TRACK_DISTANCE nothing more;  MPMHIP_TRACK_AVERAGE out_value[0] = sum_i max(eps - d_i, 0) / n;
+ *   MPMHIP_TRACK_CUBED out_value[0] = sum_i max(eps - d_i, 0)^3.
+ * nb == NULL: the index alone (NearestNeighbour of preprocess/losses/layers.py).  best_scratch [n] uint64; scratch
+ * [MPMHIP_TRACK_COLLISION_SCRATCH(n)] doubles (the two penalty modes).  n == 0: MPMHIP_OK, nothing written.  n_body must be positive. */
+#define MPMHIP_TRACK_DISTANCE 0
+#define MPMHIP_TRACK_AVERAGE 1
+#define MPMHIP_TRACK_CUBED 2
+#define MPMHIP_TRACK_COLLISION_SCRATCH(n) (((int64_t)(n) + MPMHIP_TRACK_TPB - 1) / MPMHIP_TRACK_TPB)
+int mpmhip_track_collision_forward(int32_t device, void *stream, const float *va, int32_t n, const float *vb, const float *nb, int32_t n_body,
+                                   float eps, int32_t mode, uint64_t *best_scratch, double *scratch, int32_t *out_index, float *out_distance,
+                                   float *out_value);
+/* d_va [n*3] from the forward's index and distance: -g[i] nb[j] in the distance mode (g [n]); g[0] slope nb[j] / n and
+ * g[0] 3 pen^2 nb[j] in the penalty modes (g [1]), slope = 1 where eps - d > 0, 0 where < 0 and exactly 1/2 where equal, as
+ * torch.maximum.  The body receives no gradient.  d_va == NULL: nothing launched. */
+int mpmhip_track_collision_backward(int32_t device, void *stream, int32_t n, const float *nb, int32_t n_body, const int32_t *index,
+                                    const float *distance, float eps, int32_t mode, const float *g, float *d_va);
+
 /* ---- introspection ---------------------------------------------------------------------- */
 /* dense reference-layout copies of grid_m [G^3], grid_v_in [G^3*3], grid_v_out [G^3*3] as they
  * stand after the last substep's grid stage ([dev] outputs, any may be NULL).  Synchronous. */

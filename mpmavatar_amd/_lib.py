@@ -163,6 +163,14 @@ SIGNATURES = {
     "mpmhip_image_head_bytes": (C.c_int, [C.c_int32, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]),
     "mpmhip_image_compose": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp]),
     "mpmhip_eval_pair": (C.c_int, [C.c_int32, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
+    "mpmhip_track_render_vars": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32] + [vp] * 6),
+    "mpmhip_track_render_vars_backward": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32] + [vp] * 12),
+    "mpmhip_track_face_geometry": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp]),
+    "mpmhip_track_terms_forward": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32] + [vp] * 4),
+    "mpmhip_track_terms_backward": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32] + [vp] * 9),
+    "mpmhip_track_vertex_normals": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp]),
+    "mpmhip_track_collision_forward": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_float, C.c_int32] + [vp] * 5),
+    "mpmhip_track_collision_backward": (C.c_int, [C.c_int32, vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_float, C.c_int32, vp, vp]),
     "mpmhip_dist_enable": (C.c_int, [vp]),
     "mpmhip_dist_set_ghost_mode": (C.c_int, [vp, C.c_int32]),
     "mpmhip_dist_set_mass_span": (C.c_int, [vp, C.c_float, C.c_float]),

@@ -16,6 +16,7 @@
 
 #include <cstdint>
 
+#include "block_sum.hpp"
 #include "entry.hpp"
 #include "reg_math.hpp"
 
@@ -25,28 +26,6 @@ using namespace entry;
 constexpr int TPB = MPMHIP_REG_TPB;  // the scratch-size macros of mpmhip.h count workgroups of this size
 constexpr int WAVES = TPB / 64;
 static_assert(TPB == 256 && TPB % 64 == 0, "block_sum folds four waves");
-
-// Sum of N doubles per lane over the workgroup in a fixed order: shuffles within each wave (lane l += lane l + off, off = 32 .. 1),
-// then thread 0 adds the wave sums in wave order.  Valid in thread 0 only.  Every thread of the workgroup must call it.
-template <int N>
-__device__ __forceinline__ void block_sum(double (&v)[N], double (*red)[WAVES]) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] += __shfl_down(v[i], off);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int i = 0; i < N; ++i) red[i][wave] = v[i];
-  __syncthreads();
-  if (threadIdx.x == 0)
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      v[i] = red[i][0];
-#pragma unroll
-      for (int w = 1; w < WAVES; ++w) v[i] += red[i][w];
-    }
-}
 
 // partials [gridDim.x * 3] doubles: the workgroup's sums of |m_f - 1|, the iso terms and a_f; area [F]
 __global__ __launch_bounds__(TPB) void k_mesh_rows(int n_f, int n_v, const float *__restrict__ verts, const int32_t *__restrict__ faces,

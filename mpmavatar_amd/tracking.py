@@ -1,0 +1,302 @@
+"""The mesh tracking step on the device (preprocess/train_mesh_lbs_actorshq.py and train_mesh_lbs_4ddress.py): what one iteration of
+the reference's tracking loop computes between the trained ``vertices`` and the rasteriser's argument list, and the loss terms the
+appearance loop does not have (csrc/track.hip, csrc/track_math.hpp):
+
+    fg = FaceGaussians(faces)                                                     # once per mesh
+    rendervar = fg.render_vars(vertices, log_scales, logit_opacities)             # params2rendervar :209-225, one Gaussian per face
+    area, scale, opacity = fg.losses(vertices, log_scales, logit_opacities)       # losses['area'], ['scale'], ['opacity'] :242-268
+    smplx_vn = VertexNormals(body_faces)(smplx_v)                                 # compute_vertex_normals, utils/geo_utils.py:8-19
+    collision = collision_penalty(vertices[cloth_v_idx], smplx_v, smplx_vn)       # preprocess/losses/physics.py:6-20
+
+The rest of the iteration is already here: ``rasterizer.GaussianRasterizer``, ``image_loss`` and ``l1_loss``, ``MeshRegularizer``
+(normal, iso, eq_faces_weight) and ``FusedAdam``.  INTEGRATION.md, "Before the solver: the tracking step", has the switch-over.
+
+What is pinned by the reference's own code (tests/golden/track.npz): the barycentres, the frame matrices x | y | z, the face normals
+and areas, the vertex normals, the penalty in its three modes and its nearest indices.  UNCONFIRMED: the matrix -> quaternion map,
+which restates pytorch3d.transforms.matrix_to_quaternion (pytorch3d is not installed where the fixtures are made, and its older
+releases leave the sign alone): the roots sqrt(max(0, 1 +- m00 +- m11 +- m22)), the candidate rows divided by twice the root
+floored at 0.1, the row of the largest root, then the sign that makes w >= 0.  ``q`` and ``-q`` render the same image.
+
+Rules: fp32 arithmetic, fp64 sums in a fixed order, no floating-point atomics, so the same inputs give the same bits, values and
+gradients.  The backward is the exact derivative of the forward with every discrete decision held fixed (the longest edge, the
+quaternion's branch and sign, sign(0) = 0, the hinge with slope exactly 1/2 where eps - d == 0); there is no double backward.  With
+grad mode off, or with nothing requiring grad, the same launch gives the same bits with no ``grad_fn`` and nothing saved.  A
+zero-area face gives NaN and a vertex in no face a NaN normal, as in the reference.  No CPU fallback: tensors must live on an MI355X.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _lib as L
+from ._call import call, expect, ptr, upstream, wants_grad
+from .mesh_frames import _csr
+
+_TPB = 256        # MPMHIP_TRACK_TPB
+_MODES = {"distance": 0, "average": 1, "cubed": 2}     # MPMHIP_TRACK_DISTANCE, _AVERAGE, _CUBED
+
+
+class _Mesh:
+    """faces [F, 3] checked once, and the vertex -> corner table (item = 3 f + c, ascending within a vertex), which needs the vertex
+    count and is built at its first use"""
+
+    def __init__(self, faces: torch.Tensor):
+        if not isinstance(faces, torch.Tensor) or faces.dtype not in (torch.int32, torch.int64):
+            raise RuntimeError("faces: expected an int32 or int64 tensor on the GPU")
+        self.faces = expect(faces.to(torch.int32).contiguous(), torch.int32, "faces", last=3, rows=True)
+        self.n_faces = self.faces.shape[0]
+        if int(self.faces.min()) < 0:
+            raise RuntimeError("faces: negative index")
+        self.n_verts_min = int(self.faces.max()) + 1
+        L.load()                                 # a missing library is reported here, not at the first launch
+        self._table_key = self._table_value = None
+
+    def _verts(self, verts, name="vertices"):
+        v = expect(verts, torch.float32, name, last=3)
+        if v.dim() != 2 or v.shape[0] < self.n_verts_min:
+            raise RuntimeError(f"{name}: expected [V, 3] with V >= {self.n_verts_min}, got {tuple(v.shape)}")
+        if v.device != self.faces.device:
+            raise RuntimeError(f"{name} and faces must be on the same device")
+        return v
+
+    def _table(self, n_verts):
+        if self._table_key != n_verts:
+            self._table_key, self._table_value = n_verts, _csr(self.faces, n_verts, "faces")
+        return self._table_value
+
+
+def _empty(dev, *shape):
+    return torch.empty(*shape, dtype=torch.float32, device=dev)
+
+
+def _launch_render(fg, v, ls, lo):
+    dev, n_f = v.device, fg.n_faces
+    means, rot, scales, opac = _empty(dev, n_f, 3), _empty(dev, n_f, 4), _empty(dev, n_f, 3), _empty(dev, n_f, 1)
+    call("mpmhip_track_render_vars", dev, v.data_ptr(), v.shape[0], fg.faces.data_ptr(), n_f, ls.data_ptr(), lo.data_ptr(), means.data_ptr(),
+         rot.data_ptr(), scales.data_ptr(), opac.data_ptr())
+    return means, rot, scales, opac
+
+
+def _grads(ctx, v, ls, lo):
+    """(d_verts, d_log_scales, d_logit_opacities) to be written, None where not wanted, and the table and stencil d_verts needs"""
+    fg = ctx.fg
+    d_v, d_ls, d_lo = [torch.empty_like(t) if want else None for want, t in zip(ctx.needs_input_grad[:3], (v, ls, lo))]
+    start, items, stencil = None, None, None
+    if d_v is not None:
+        start, items = fg._table(v.shape[0])
+        stencil = _empty(v.device, fg.n_faces, 3, 3)
+    return d_v, d_ls, d_lo, start, items, stencil
+
+
+class _RenderVars(torch.autograd.Function):
+    """(vertices, log_scales, logit_opacities) -> (means3D, rotations, scales, opacities)"""
+
+    @staticmethod
+    def forward(ctx, v, ls, lo, fg):
+        out = _launch_render(fg, v, ls, lo)
+        ctx.fg = fg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(v, ls, lo)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_means, g_rot, g_scales, g_opac):
+        v, ls, lo = ctx.saved_tensors
+        fg = ctx.fg
+        g = [upstream(t) for t in (g_means, g_rot, g_scales, g_opac)]
+        if all(t is None for t in g):
+            return None, None, None, None
+        d_v, d_ls, d_lo, start, items, stencil = _grads(ctx, v, ls, lo)
+        call("mpmhip_track_render_vars_backward", v.device, v.data_ptr(), v.shape[0], fg.faces.data_ptr(), fg.n_faces, ls.data_ptr(),
+             lo.data_ptr(), *[ptr(t) for t in g], ptr(start), ptr(items), ptr(stencil), ptr(d_v), ptr(d_ls), ptr(d_lo))
+        return d_v, d_ls, d_lo, None
+
+
+def _launch_terms(fg, v, ls, lo):
+    dev = v.device
+    terms = _empty(dev, 3)
+    scratch = torch.empty(3 * ((fg.n_faces + _TPB - 1) // _TPB), dtype=torch.float64, device=dev)
+    call("mpmhip_track_terms_forward", dev, v.data_ptr(), v.shape[0], fg.faces.data_ptr(), fg.n_faces, ls.data_ptr(), lo.data_ptr(),
+         scratch.data_ptr(), terms.data_ptr())
+    return terms
+
+
+class _Terms(torch.autograd.Function):
+    """(vertices, log_scales, logit_opacities) -> [area, scale, opacity]"""
+
+    @staticmethod
+    def forward(ctx, v, ls, lo, fg):
+        terms = _launch_terms(fg, v, ls, lo)
+        ctx.fg = fg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(v, ls, lo)
+        return terms
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_terms):
+        v, ls, lo = ctx.saved_tensors
+        fg = ctx.fg
+        g = upstream(g_terms)
+        if g is None:
+            return None, None, None, None
+        d_v, d_ls, d_lo, start, items, stencil = _grads(ctx, v, ls, lo)
+        call("mpmhip_track_terms_backward", v.device, v.data_ptr(), v.shape[0], fg.faces.data_ptr(), fg.n_faces, ls.data_ptr(), lo.data_ptr(),
+             g.data_ptr(), ptr(start), ptr(items), ptr(stencil), ptr(d_v), ptr(d_ls), ptr(d_lo))
+        return d_v, d_ls, d_lo, None
+
+
+class FaceGaussians(_Mesh):
+    """One Gaussian per face of one mesh: the four computed entries of ``params2rendervar`` and the loss terms on them.  faces [F, 3]
+    (int32 or int64); vertices [V, 3] with V beyond the largest index; log_scales [F, 3]; logit_opacities [F, 1] or [F]."""
+
+    def _inputs(self, vertices, log_scales, logit_opacities):
+        v = self._verts(vertices)
+        ls = expect(log_scales, torch.float32, "log_scales", shape=(self.n_faces, 3))
+        lo = expect(logit_opacities, torch.float32, "logit_opacities")
+        if tuple(lo.shape) not in ((self.n_faces, 1), (self.n_faces,)):
+            raise RuntimeError(f"logit_opacities: expected shape {(self.n_faces, 1)}, got {tuple(lo.shape)}")
+        if not (ls.device == lo.device == v.device):
+            raise RuntimeError("FaceGaussians: the tensors must be on the same device")
+        return v, ls, lo
+
+    def render_vars(self, vertices, log_scales, logit_opacities) -> dict:
+        """-> {means3D [F, 3], rotations [F, 4] WXYZ, scales [F, 3], opacities [F, 1]}; ``colors_precomp`` and ``means2D`` are the
+        caller's.  The quaternion conversion is UNCONFIRMED against pytorch3d (module docstring); ``q`` and ``-q`` render alike."""
+        v, ls, lo = self._inputs(vertices, log_scales, logit_opacities)
+        out = _RenderVars.apply(v, ls, lo, self) if wants_grad(v, ls, lo) else _launch_render(self, v, ls, lo)
+        return dict(zip(("means3D", "rotations", "scales", "opacities"), out))
+
+    def terms(self, vertices, log_scales, logit_opacities) -> torch.Tensor:
+        """-> the [3] tensor (area, scale, opacity), for callers who weight with a tensor product"""
+        v, ls, lo = self._inputs(vertices, log_scales, logit_opacities)
+        return _Terms.apply(v, ls, lo, self) if wants_grad(v, ls, lo) else _launch_terms(self, v, ls, lo)
+
+    def losses(self, vertices, log_scales, logit_opacities):
+        """-> (area, scale, opacity): 0-dim fp32 tensors"""
+        return self.terms(vertices, log_scales, logit_opacities).unbind(0)
+
+    def _geometry(self, vertices, normals, areas):
+        v = self._verts(vertices).detach()
+        call("mpmhip_track_face_geometry", v.device, v.data_ptr(), v.shape[0], self.faces.data_ptr(), self.n_faces, ptr(normals), ptr(areas))
+
+    def face_normals(self, vertices) -> torch.Tensor:
+        """compute_face_normals -> [F, 3]; forward only"""
+        out = _empty(self.faces.device, self.n_faces, 3)
+        self._geometry(vertices, out, None)
+        return out
+
+    def face_areas(self, vertices) -> torch.Tensor:
+        """compute_face_areas -> [F]; forward only"""
+        out = _empty(self.faces.device, self.n_faces)
+        self._geometry(vertices, None, out)
+        return out
+
+
+class VertexNormals(_Mesh):
+    """compute_vertex_normals for one mesh: the unnormalised ``cross(v0 - v1, v2 - v1)`` of every incident face, summed per vertex in
+    ascending face order (a gather, not an ``index_add_``: the same bits on every run) and normalised.  Forward only -- the body's
+    normals take no gradient in the tracking loop (``collision_penalty``).  A vertex in no face gives NaN, as in the reference."""
+
+    def __call__(self, verts: torch.Tensor) -> torch.Tensor:
+        v = self._verts(verts, "verts").detach()
+        start, items = self._table(v.shape[0])
+        out = torch.empty_like(v)
+        call("mpmhip_track_vertex_normals", v.device, v.data_ptr(), v.shape[0], self.faces.data_ptr(), self.n_faces, start.data_ptr(),
+             items.data_ptr(), out.data_ptr())
+        return out
+
+
+def vertex_normals(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """``compute_vertex_normals(vertices, faces)``; builds the vertex -> face table on every call (``VertexNormals`` keeps it)"""
+    return VertexNormals(faces)(verts)
+
+
+def _launch_collision(va, vb, nb, eps, mode):
+    """-> (index int32 [n], distance [n] or None, value [1] or None)"""
+    dev, n = va.device, va.shape[0]
+    index = torch.empty(n, dtype=torch.int32, device=dev)
+    dist = None if nb is None else _empty(dev, n)
+    reduce = nb is not None and mode != _MODES["distance"]
+    value = _empty(dev, 1) if reduce else None
+    if n > 0:
+        best = torch.empty(n, dtype=torch.int64, device=dev)
+        scratch = torch.empty((n + _TPB - 1) // _TPB, dtype=torch.float64, device=dev) if reduce else None
+        call("mpmhip_track_collision_forward", dev, va.data_ptr(), n, vb.data_ptr(), ptr(nb), vb.shape[0], eps, mode, best.data_ptr(),
+             ptr(scratch), index.data_ptr(), ptr(dist), ptr(value))
+    elif reduce:                                 # the reference's 0 / 0 and its empty sum
+        value.fill_(float("nan") if mode == _MODES["average"] else 0.0)
+    return index, dist, value
+
+
+class _Collision(torch.autograd.Function):
+    """va -> the distances or the penalty; the body is constant"""
+
+    @staticmethod
+    def forward(ctx, va, vb, nb, eps, mode):
+        index, dist, value = _launch_collision(va, vb, nb, eps, mode)
+        ctx.eps, ctx.mode = eps, mode
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(nb, index, dist)
+        ctx.mark_non_differentiable(index)
+        return (dist if value is None else value.reshape(())), index
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out, _g_index):
+        nb, index, dist = ctx.saved_tensors
+        n = index.shape[0]
+        g = upstream(g_out, (n,) if ctx.mode == _MODES["distance"] else None)
+        if g is None:
+            return None, None, None, None, None
+        d_va = _empty(nb.device, n, 3)
+        if n > 0:
+            call("mpmhip_track_collision_backward", nb.device, n, nb.data_ptr(), nb.shape[0], index.data_ptr(), dist.data_ptr(), ctx.eps,
+                 ctx.mode, g.data_ptr(), d_va.data_ptr())
+        return d_va, None, None, None, None
+
+
+def _points(va, vb, nb=None):
+    a = expect(va, torch.float32, "va", last=3)
+    if a.dim() != 2:
+        raise RuntimeError("va: expected an [n, 3] tensor")
+    b = expect(vb, torch.float32, "vb", last=3, rows=True)
+    if nb is not None:
+        nb = expect(nb, torch.float32, "nb", shape=tuple(b.shape))
+    for name, t in (("vb", b), ("nb", nb)):
+        if t is not None and (t.device != a.device):
+            raise RuntimeError(f"va and {name} must be on the same device")
+        if t is not None and t.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f"{name} requires grad: the body takes no gradient here (the reference runs with --lr_smplx 0.0); "
+                               f"pass {name}.detach()")
+    L.load()
+    return a, b, nb
+
+
+def collision_penalty(va, vb, nb, eps=1e-3, return_average=True, return_distance=False):
+    """``collision_penalty`` of preprocess/losses/physics.py: va [n, 3] the cloth vertices, vb [m, 3] and nb [m, 3] the body's vertices
+    and vertex normals.  With j the nearest body vertex of va[i] and d_i = -nb[j] . (va[i] - vb[j]):
+
+        return_distance                  -> the [n] signed distances d
+        return_average (the default)     -> sum(max(eps - d, 0)) / n
+        neither                          -> sum(max(eps - d, 0) ** 3)
+
+    The nearest vertex is found without the [n, m] distance matrix, by the kernel of ``geo_metrics``' nearest-neighbour search: the
+    lowest index of the exact minimum of the direct-form squared distance |a - b|^2.  The reference takes the argmin of the expanded
+    form |a|^2 + |b|^2 - 2 a.b; where the two decide a near-tie differently, the expanded form is the less accurate of the two.
+    The gradient goes to ``va`` alone: ``slope * nb[j] / n`` (slope 1 where eps - d > 0, 0 where < 0, exactly 1/2 where equal, as
+    ``torch.maximum``), ``3 pen^2 nb[j]`` in the cubed mode, ``-g_i nb[j]`` in the distance mode.  A ``vb`` or ``nb`` that requires
+    grad raises: pass ``.detach()``."""
+    a, b, nrm = _points(va, vb, nb)
+    mode = _MODES["distance"] if return_distance else _MODES["average"] if return_average else _MODES["cubed"]
+    if wants_grad(a):
+        return _Collision.apply(a, b, nrm, float(eps), mode)[0]
+    _, dist, value = _launch_collision(a, b, nrm, float(eps), mode)
+    return dist if value is None else value.reshape(())
+
+
+def nearest_neighbour(A, B) -> torch.Tensor:
+    """``NearestNeighbour()(A, B)`` of preprocess/losses/layers.py: the int32 [n] index of the nearest row of B [m, 3] for every row of
+    A [n, 3] (the lowest index on an exact tie)."""
+    a, b, _ = _points(A.detach() if isinstance(A, torch.Tensor) else A, B.detach() if isinstance(B, torch.Tensor) else B)
+    return _launch_collision(a, b, None, 0.0, _MODES["distance"])[0]
