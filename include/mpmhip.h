@@ -913,6 +913,47 @@ int mpmhip_track_collision_forward(int32_t device, void *stream, const float *va
 int mpmhip_track_collision_backward(int32_t device, void *stream, int32_t n, const float *nb, int32_t n_body, const int32_t *index,
                                     const float *distance, float eps, int32_t mode, const float *g, float *d_va);
 
+/* ---- re-posing: k nearest neighbours and linear-blend skinning (utils/smplx_deformer.py:164-337) ------------------------------------
+ * What the reference's drivers do with SmplxDeformer between a tracked mesh and the solver's input (train_material_params.py:335-349,
+ * preprocess/train_mesh_lbs_actorshq.py:495-516), without pytorch3d or open3d.  Stand-alone maps on [dev] arrays; nothing allocates
+ * or synchronises; fp32, no atomics, fixed summation orders: the same input gives the same bits.  The SMPL-X forward is the caller's:
+ * A is smplx_output.transform_mat.
+ *
+ * mpmhip_knn (find_k_closest_verts :164-185 = pytorch3d's knn_points; o3d_knn of preprocess/helpers.py:84-94; knn_points(K=1) of
+ * lbs_weights_inpainting_*.py:60): for every query [n*dim] the k targets [m*dim] of smallest direct-form squared distance
+ * sum_d (q_d - t_d)^2 (ascending d), brute force and exact, ordered ascending by (distance, index): equal distances go to the lower
+ * index.  dim is 3 or 6, 1 <= k <= min(m, 16).  out_dists [n*k], out_idx [n*k].  The targets are cut into `slices` parts (0: chosen by
+ * the library) that are searched by different workgroups and merged by the total order of the keys (bits of d2) << 32 | index, so
+ * the result does not depend on `slices`.  scratch [scratch_len] uint64 with scratch_len >= what mpmhip_knn_scratch reports for the
+ * same n, m, dim, k and slices (it needs no device).  Non-finite input: unspecified values, indices in [0, m).  n == 0: MPMHIP_OK. */
+int mpmhip_knn_scratch(int32_t n, int32_t m, int32_t dim, int32_t k, int32_t slices, int64_t *out_len);
+int mpmhip_knn(int32_t device, void *stream, const float *queries, int32_t n, const float *targets, int32_t m, int32_t dim, int32_t k,
+               int32_t slices, uint64_t *scratch, int64_t scratch_len, float *out_dists, int32_t *out_idx);
+/* weights_from_k_closest_verts (:187-205) and the gather of transform_to_t_pose (:235-241) in one launch, from the output of
+ * mpmhip_knn: w_k = clamp(dists[p, k], 1e-8)^-power / sum_k, out_w[p, :] = sum_k w_k lbs_weights[idx[p, k], :], both sums in ascending
+ * k.  lbs_weights [n_verts*n_joints], out_w [n*n_joints]; power >= 0 (the reference uses 2); an index outside [0, n_verts) is clamped.
+ * lbs_weights == NULL: out_w [n*k] = the weights w themselves (what weights_from_k_closest_verts returns); idx, n_verts and n_joints
+ * are then not used. */
+int mpmhip_shepard_weights(int32_t device, void *stream, const float *dists, const int32_t *idx, int32_t n, int32_t k, int32_t power,
+                           const float *lbs_weights, int32_t n_verts, int32_t n_joints, float *out_w);
+/* Linear-blend skinning.  For frame b and point p: T = sum_j w[p, j] A[b, j] (all 16 entries, ascending j).
+ *   mpmhip_skin_to_pose  (transform_to_pose :290-337)    out = (T (v, 1))[:3], then + transl[b], then * scale, each only if given
+ *   mpmhip_skin_to_tpose (transform_to_t_pose :262-286)  v' = v / scale - transl[b], out = (T^-1 (v', 1))[:3]; T^-1 is the general
+ *                        4 x 4 inverse by cofactors (the last row of T is (0, 0, 0, sum_j w_j), not (0, 0, 0, 1)); a singular T
+ *                        gives non-finite output
+ * verts [n_points*3], or [n_frames*n_points*3] with verts_batched; w [n_points*n_joints], or one such block per frame with w_batched
+ * (the reference's lbs_w.repeat is never needed); A [n_frames*n_joints*16]; transl [n_frames*3] or NULL; scale [1], or [n_frames]
+ * with scale_batched, or NULL, on the device.  out_points [n_frames*n_points*3]; out_T [n_frames*n_points*16] (T, or T^-1 on the way
+ * to the T-pose, which is what the reference returns) or NULL = not written.  1 <= n_joints <= MPMHIP_SKIN_MAX_JOINTS.
+ * n_frames == 0 or n_points == 0: MPMHIP_OK. */
+#define MPMHIP_SKIN_MAX_JOINTS 127
+int mpmhip_skin_to_pose(int32_t device, void *stream, const float *verts, int32_t verts_batched, const float *w, int32_t w_batched,
+                        const float *A, int32_t n_frames, int32_t n_points, int32_t n_joints, const float *transl, const float *scale,
+                        int32_t scale_batched, float *out_points, float *out_T);
+int mpmhip_skin_to_tpose(int32_t device, void *stream, const float *verts, int32_t verts_batched, const float *w, int32_t w_batched,
+                         const float *A, int32_t n_frames, int32_t n_points, int32_t n_joints, const float *transl, const float *scale,
+                         int32_t scale_batched, float *out_points, float *out_T);
+
 /* ---- introspection ---------------------------------------------------------------------- */
 /* dense reference-layout copies of grid_m [G^3], grid_v_in [G^3*3], grid_v_out [G^3*3] as they
  * stand after the last substep's grid stage ([dev] outputs, any may be NULL).  Synchronous. */

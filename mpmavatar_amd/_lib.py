@@ -171,6 +171,11 @@ SIGNATURES = {
     "mpmhip_track_vertex_normals": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp]),
     "mpmhip_track_collision_forward": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_float, C.c_int32] + [vp] * 5),
     "mpmhip_track_collision_backward": (C.c_int, [C.c_int32, vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_float, C.c_int32, vp, vp]),
+    "mpmhip_knn_scratch": (C.c_int, [C.c_int32] * 5 + [C.POINTER(C.c_int64)]),
+    "mpmhip_knn": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64, vp, vp]),
+    "mpmhip_shepard_weights": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp]),
+    "mpmhip_skin_to_pose": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp]),
+    "mpmhip_skin_to_tpose": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp]),
     "mpmhip_dist_enable": (C.c_int, [vp]),
     "mpmhip_dist_set_ghost_mode": (C.c_int, [vp, C.c_int32]),
     "mpmhip_dist_set_mass_span": (C.c_int, [vp, C.c_float, C.c_float]),
