@@ -43,6 +43,18 @@ def expect(t, dtype, name, *, shape=None, last=None, rows=False, contiguous=True
     return t
 
 
+def csr(keys, n_keys, what):
+    """key -> items table on the device: (start [n_keys + 1] int32, items int32 in ascending item index within a key).  Plumbing for
+    the serial reductions of the backward passes, built with torch ops; the bounds of ``keys`` are checked here, once."""
+    k = keys.reshape(-1).long()
+    counts = torch.bincount(k, minlength=n_keys)          # raises on a negative key
+    if counts.numel() != n_keys:
+        raise RuntimeError(f"{what}: index {counts.numel() - 1} out of range [0, {n_keys})")
+    start = torch.zeros(n_keys + 1, dtype=torch.int32, device=keys.device)
+    start[1:] = torch.cumsum(counts, 0)
+    return start, torch.sort(k, stable=True).indices.to(torch.int32)
+
+
 def wants_grad(*tensors):
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 

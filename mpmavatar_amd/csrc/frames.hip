@@ -5,79 +5,38 @@
 // per-Gaussian maps, HBM-bound: 24 B of indices + gathered vertices in, 68 B out per face; 36 B in + 32 B of gathered
 // frame, 44 B out per Gaussian.  Keeps the simulated vertices on the device instead of the reference's
 // OBJ -> disk -> Blender -> reload detour for everything but the AO map.
+// k_face_frames is one thread per item over frames_math.hpp (shared with the backward and the host build).  The bodies of
+// k_bind_gaussians, k_render_inputs and k_cov_from_F are NOT in that header yet, on purpose: their outputs feed every golden
+// comparison downstream, and the instructions the compiler emits for them follow the shape of the source, not only its expression
+// trees.  Tried, each compared against this file's device listing: the two per-Gaussian bodies as one shared row function
+// (rotations moved by up to 65536 ulp on random unit-scale inputs, means and scales stayed bitwise equal), the bodies moved
+// verbatim into inline functions (listing differs in scheduling and address code), and the Hamilton product alone as a shared
+// function (listing differs).  Only the vector type and the clamp constant are shared here; that leaves the listing identical.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "entry.hpp"
+#include "frames_math.hpp"
 
 namespace {
 
 using namespace entry;
 constexpr int TPB = 256;
 
-struct F3 { float x, y, z; };
-__device__ __forceinline__ F3 ld3(const float *p, int i) { return F3{p[3 * (size_t)i], p[3 * (size_t)i + 1], p[3 * (size_t)i + 2]}; }
-__device__ __forceinline__ F3 sub(F3 a, F3 b) { return F3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ F3 cross(F3 a, F3 b) { return F3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ float dot(F3 a, F3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-// graphics_utils.py:82-86: x / sqrt(clamp(dot(x, x), min = 1e-20))
-__device__ __forceinline__ float length(F3 a) { return sqrtf(fmaxf(dot(a, a), 1e-20f)); }
-__device__ __forceinline__ F3 safe_normalize(F3 a) { float l = length(a); return F3{a.x / l, a.y / l, a.z / l}; }
-
-// roma.rotmat_to_unitquat (= SciPy's Rotation.from_matrix): XYZW, the largest of (R00, R11, R22, trace) picks the
-// branch (first maximum wins, like argmax), no sign canonicalisation
-__device__ __forceinline__ void rotmat_to_quat_xyzw(const float R[3][3], float q[4]) {
-  float d[4] = {R[0][0], R[1][1], R[2][2], 0.0f};
-  d[3] = d[0] + d[1] + d[2];
-  int c = 0;
-  for (int k = 1; k < 4; ++k)
-    if (d[k] > d[c]) c = k;
-  if (c != 3) {
-    int i = c, j = (i + 1) % 3, k = (j + 1) % 3;
-    q[i] = 1.0f - d[3] + 2.0f * R[i][i];
-    q[j] = R[j][i] + R[i][j];
-    q[k] = R[k][i] + R[i][k];
-    q[3] = R[k][j] - R[j][k];
-  } else {
-    q[0] = R[2][1] - R[1][2];
-    q[1] = R[0][2] - R[2][0];
-    q[2] = R[1][0] - R[0][1];
-    q[3] = 1.0f + d[3];
-  }
-  float n = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  for (int k = 0; k < 4; ++k) q[k] = q[k] / n;
-}
+using frm::V3;
+using frm::ld3;
 
 __global__ void k_face_frames(const float *verts, const int32_t *faces, int n_f, float *center, float *mat, float *quat,
                               float *scale) {
   int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= n_f) return;
-  int i0 = faces[3 * (size_t)f], i1 = faces[3 * (size_t)f + 1], i2 = faces[3 * (size_t)f + 2];
-  F3 v0 = ld3(verts, i0), v1 = ld3(verts, i1), v2 = ld3(verts, i2);
-  // triangles.mean(dim=-2): ((v0 + v1) + v2) / 3
-  center[3 * (size_t)f] = ((v0.x + v1.x) + v2.x) / 3.0f;
-  center[3 * (size_t)f + 1] = ((v0.y + v1.y) + v2.y) / 3.0f;
-  center[3 * (size_t)f + 2] = ((v0.z + v1.z) + v2.z) / 3.0f;
-  F3 e1 = sub(v1, v0), e2 = sub(v2, v0);
-  F3 a0 = safe_normalize(e1);
-  F3 a1 = safe_normalize(cross(a0, e2));
-  F3 a2 = safe_normalize(cross(a1, a0));
-  a2 = F3{-a2.x, -a2.y, -a2.z};  // "will have artifacts without negation", graphics_utils.py:99
-  float R[3][3] = {{a0.x, a1.x, a2.x}, {a0.y, a1.y, a2.y}, {a0.z, a1.z, a2.z}};  // columns a0 a1 a2
-  float *m = mat + 9 * (size_t)f;
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) m[3 * r + c] = R[r][c];
-  scale[f] = (length(e1) + fabsf(dot(a2, e2))) / 2.0f;
-  float q[4];
-  rotmat_to_quat_xyzw(R, q);
-  float *o = quat + 4 * (size_t)f;  // stored WXYZ (quat_xyzw_to_wxyz)
-  o[0] = q[3]; o[1] = q[0]; o[2] = q[1]; o[3] = q[2];
+  frm::face_frame_row(f, verts, faces, center, mat, quat, scale);
 }
 
 // torch.nn.functional.normalize(q, dim=-1): q / max(|q|, 1e-12)
 __device__ __forceinline__ void normalize4(float q[4]) {
-  float n = fmaxf(sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]), 1e-12f);
+  float n = fmaxf(sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]), frm::NORM_EPS);
   for (int k = 0; k < 4; ++k) q[k] = q[k] / n;
 }
 
@@ -90,7 +49,7 @@ __global__ void k_bind_gaussians(int n_g, const int32_t *binding, const float *x
   float s = fscale[f];
   if (xyz) {  // bmm(face_orien_mat[binding], _xyz) * face_scaling + face_center, gaussian_model.py:149-150
     const float *m = mat + 9 * (size_t)f;
-    F3 p = ld3(xyz_local, g), c = ld3(center, f);
+    V3 p = ld3(xyz_local, g), c = ld3(center, f);
     xyz[3 * (size_t)g] = (m[0] * p.x + m[1] * p.y + m[2] * p.z) * s + c.x;
     xyz[3 * (size_t)g + 1] = (m[3] * p.x + m[4] * p.y + m[5] * p.z) * s + c.y;
     xyz[3 * (size_t)g + 2] = (m[6] * p.x + m[7] * p.y + m[8] * p.z) * s + c.z;
@@ -133,7 +92,7 @@ __global__ void k_render_inputs(int n_g, int n_x, const int32_t *binding, const 
   int f = binding[g];
   float s = fscale[f];
   const float *m = mat + 9 * (size_t)f;
-  F3 p = ld3(xyz_local, g), c = ld3(center, f);
+  V3 p = ld3(xyz_local, g), c = ld3(center, f);
   means3D[3 * (size_t)g] = (m[0] * p.x + m[1] * p.y + m[2] * p.z) * s + c.x;
   means3D[3 * (size_t)g + 1] = (m[3] * p.x + m[4] * p.y + m[5] * p.z) * s + c.y;
   means3D[3 * (size_t)g + 2] = (m[6] * p.x + m[7] * p.y + m[8] * p.z) * s + c.z;

@@ -1,5 +1,6 @@
-// frames_grad_math.hpp -- the backward pass of frames.hip: the exact derivative of k_face_frames and of the binding
-// expressions of k_bind_gaussians / k_render_inputs as those kernels compute them, with every discrete decision held fixed
+// frames_grad_math.hpp -- the backward pass of frames.hip: the exact derivative of frm::face_frame_row (frames_math.hpp, whose
+// pieces it calls where it needs the per-face forward's values) and of the binding expressions of k_bind_gaussians /
+// k_render_inputs as those kernels compute them, with every discrete decision held fixed
 // (the rasteriser's policy, raster_grad_math.hpp): the quaternion branch, the sign inside fabsf (sign(0) = 0), and the three
 // clamps -- max(dot, 1e-20) inside length(), max(|q|, 1e-12) inside normalize4() -- which pass zero slope to the clamped
 // quantity where they bind.  Plain C++ for the device (frames_backward.hip) and the host (tests/hostframes_grad/) alike: one
@@ -14,26 +15,19 @@
 // Forward, per face: e1 = v1 - v0, e2 = v2 - v0, a0 = e1 / |e1|, a1 = (a0 x e2) / |.|, a2 = -(a1 x a0) / |.|, M = [a0 a1 a2],
 // s = (|e1| + |a2 . e2|) / 2, c = (v0 + v1 + v2) / 3, Q = rotmat_to_unitquat(M).  The backward walks that chain in reverse.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <math.h>
-#include <stdint.h>
+#include "frames_math.hpp"
 
 namespace fgrad {
 
-struct V3 {
-  float x, y, z;
-};
-
-__host__ __device__ __forceinline__ V3 ld3(const float *p, int64_t i) { return V3{p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
-__host__ __device__ __forceinline__ V3 sub(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__host__ __device__ __forceinline__ V3 add(V3 a, V3 b) { return V3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-__host__ __device__ __forceinline__ V3 mul(V3 a, float s) { return V3{a.x * s, a.y * s, a.z * s}; }
-__host__ __device__ __forceinline__ V3 cross(V3 a, V3 b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__host__ __device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-
-constexpr float LEN_EPS = 1e-20f;   // graphics_utils.py:82-86, length(): sqrt(clamp(dot(x, x), min = 1e-20))
-constexpr float NORM_EPS = 1e-12f;  // torch.nn.functional.normalize: x / max(|x|, 1e-12)
+using frm::V3;
+using frm::add;
+using frm::cross;
+using frm::dot;
+using frm::ld3;
+using frm::mul;
+using frm::sub;
+using frm::LEN_EPS;
+using frm::normalize4;
 
 // u = x / l with l = sqrt(max(x . x, 1e-20)): d x from d u.  Free clamp: (d u - u (u . d u)) / l; bound clamp: l is a constant.
 __host__ __device__ __forceinline__ V3 safe_normalize_backward(V3 x, V3 du, V3 &u, float &l) {
@@ -45,13 +39,7 @@ __host__ __device__ __forceinline__ V3 safe_normalize_backward(V3 x, V3 du, V3 &
   return V3{(du.x - u.x * along) / l, (du.y - u.y * along) / l, (du.z - u.z * along) / l};
 }
 
-// u = q / max(|q|, 1e-12) (normalize4 of frames.hip): u out, and d q from d u
-__host__ __device__ __forceinline__ void normalize4(const float q[4], float u[4], float &n, bool &bound) {
-  float len = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  bound = len < NORM_EPS;
-  n = fmaxf(len, NORM_EPS);
-  for (int k = 0; k < 4; ++k) u[k] = q[k] / n;
-}
+// u = q / n (frm::normalize4, or the unclamped q / |q| of the matrix -> quaternion map): d q from d u
 __host__ __device__ __forceinline__ void normalize4_backward(const float u[4], float n, bool bound, const float du[4], float dq[4]) {
   float along = bound ? 0.0f : u[0] * du[0] + u[1] * du[1] + u[2] * du[2] + u[3] * du[3];
   for (int k = 0; k < 4; ++k) dq[k] = (du[k] - u[k] * along) / n;
@@ -174,25 +162,11 @@ __host__ __device__ __forceinline__ void face_frames_backward(int64_t f, const f
     float R[3][3];
     for (int r = 0; r < 3; ++r)
       for (int c = 0; c < 3; ++c) R[r][c] = mat_saved[9 * f + 3 * r + c];
-    float d[4] = {R[0][0], R[1][1], R[2][2], 0.0f};
-    d[3] = d[0] + d[1] + d[2];
-    int b = 0;
-    for (int k = 1; k < 4; ++k)
-      if (d[k] > d[b]) b = k;
-    int i = b, j = (i + 1) % 3, k = (j + 1) % 3;
-    float q[4];  // XYZW before the normalisation, as rotmat_to_quat_xyzw forms it
-    if (b != 3) {
-      q[i] = 1.0f - d[3] + 2.0f * R[i][i];
-      q[j] = R[j][i] + R[i][j];
-      q[k] = R[k][i] + R[i][k];
-      q[3] = R[k][j] - R[j][k];
-    } else {
-      q[0] = R[2][1] - R[1][2];
-      q[1] = R[0][2] - R[2][0];
-      q[2] = R[1][0] - R[0][1];
-      q[3] = 1.0f + d[3];
-    }
-    float n = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const int b = frm::quat_branch(R);
+    const int i = b, j = (i + 1) % 3, k = (j + 1) % 3;
+    float q[4];  // XYZW before the normalisation
+    frm::quat_numerators(R, b, q);
+    const float n = frm::norm4(q);
     const float *qs = quat_saved + 4 * f, *gq = g_quat + 4 * f;
     float u[4] = {qs[1], qs[2], qs[3], qs[0]}, du[4] = {gq[1], gq[2], gq[3], gq[0]}, dq[4];  // WXYZ -> XYZW
     normalize4_backward(u, n, false, du, dq);  // q / n, no clamp in this one
@@ -209,16 +183,8 @@ __host__ __device__ __forceinline__ void face_frames_backward(int64_t f, const f
     }
   }
   V3 da0{dR[0][0], dR[1][0], dR[2][0]}, da1{dR[0][1], dR[1][1], dR[2][1]}, da2{dR[0][2], dR[1][2], dR[2][2]};
-  // the forward chain again
-  V3 e1 = sub(v1, v0), e2 = sub(v2, v0);
-  float l1sq = dot(e1, e1), l1 = sqrtf(fmaxf(l1sq, LEN_EPS));
-  V3 a0{e1.x / l1, e1.y / l1, e1.z / l1};
-  V3 c1 = cross(a0, e2);
-  float lc1 = sqrtf(fmaxf(dot(c1, c1), LEN_EPS));
-  V3 a1{c1.x / lc1, c1.y / lc1, c1.z / lc1};
-  V3 c2 = cross(a1, a0);
-  float lc2 = sqrtf(fmaxf(dot(c2, c2), LEN_EPS));
-  V3 a2{-(c2.x / lc2), -(c2.y / lc2), -(c2.z / lc2)};
+  const frm::FaceChain ch = frm::face_chain(v0, v1, v2);  // the forward's own values; the walk back starts here
+  const V3 e1 = ch.e1, e2 = ch.e2, a0 = ch.a0, c1 = ch.c1, a1 = ch.a1, c2 = ch.c2, a2 = ch.a2;
   // s = (|e1| + |t|) / 2, t = a2 . e2
   float dl1 = 0.0f;
   V3 de2{0.0f, 0.0f, 0.0f};
@@ -242,7 +208,7 @@ __host__ __device__ __forceinline__ void face_frames_backward(int64_t f, const f
   de2 = add(de2, cross(dc1, a0));
   // a0 = e1 / |e1|, and |e1| inside the scale
   V3 de1 = safe_normalize_backward(e1, da0, un, ln);
-  if (!(l1sq < LEN_EPS)) de1 = add(de1, mul(a0, dl1));
+  if (!(dot(e1, e1) < LEN_EPS)) de1 = add(de1, mul(a0, dl1));
   V3 gc{0.0f, 0.0f, 0.0f};
   if (g_center) gc = V3{g_center[3 * f] / 3.0f, g_center[3 * f + 1] / 3.0f, g_center[3 * f + 2] / 3.0f};
   float *o = d_corner + 9 * f;

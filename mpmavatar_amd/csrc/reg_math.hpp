@@ -29,16 +29,10 @@ constexpr int K = 3;             // neighbours per face
 constexpr int STENCIL = 1 + K;   // faces a row touches
 constexpr int ROW = STENCIL * 9; // floats of d_stencil per face
 
-struct V3 {
-  float x, y, z;
-};
-
-__host__ __device__ __forceinline__ V3 operator+(V3 a, V3 b) { return V3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-__host__ __device__ __forceinline__ V3 operator-(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__host__ __device__ __forceinline__ V3 operator*(float s, V3 a) { return V3{s * a.x, s * a.y, s * a.z}; }
-__host__ __device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__host__ __device__ __forceinline__ V3 cross(V3 a, V3 b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__host__ __device__ __forceinline__ float sign(float x) { return (float)(x > 0.f) - (float)(x < 0.f); }
+using frm::V3;  // with its operators + - *, found through the type
+using frm::cross;
+using frm::dot;
+using frm::sign;
 
 struct Face {
   V3 d1, d2, n, c;  // the two edges from v1, the unit normal, the centre

@@ -29,20 +29,20 @@
 
 namespace trk {
 
-using fgrad::V3;
-using fgrad::add;
-using fgrad::cross;
-using fgrad::dot;
-using fgrad::ld3;
-using fgrad::mul;
-using fgrad::sub;
+using frm::V3;
+using frm::add;
+using frm::cross;
+using frm::dot;
+using frm::ld3;
+using frm::mul;
+using frm::sign;
+using frm::st3;
+using frm::sub;
 
 constexpr float PI_F = 3.14159265358979323846f;
 constexpr int MODE_DISTANCE = 0, MODE_AVERAGE = 1, MODE_CUBED = 2;  // collision_penalty's three returns
 
-__host__ __device__ __forceinline__ float sign(float x) { return (float)(x > 0.f) - (float)(x < 0.f); }
 __host__ __device__ __forceinline__ float sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-__host__ __device__ __forceinline__ void st3(float *p, int64_t i, V3 v) { p[3 * i] = v.x; p[3 * i + 1] = v.y; p[3 * i + 2] = v.z; }
 __host__ __device__ __forceinline__ V3 nan3() { return V3{NAN, NAN, NAN}; }
 
 // the three corners of face f; false (and NaN corners) where an index is outside [0, n_verts)

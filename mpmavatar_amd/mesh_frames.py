@@ -22,19 +22,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib as L
-from ._call import call, expect, ptr, upstream, wants_grad
-
-
-def _csr(keys, n_keys, what):
-    """key -> items table on the device: (start [n_keys + 1] int32, items int32 in ascending item index within a key).  Plumbing for
-    the two reductions of the backward pass, built with torch ops; the bounds of ``keys`` are checked here, once."""
-    k = keys.reshape(-1).long()
-    counts = torch.bincount(k, minlength=n_keys)          # raises on a negative key
-    if counts.numel() != n_keys:
-        raise RuntimeError(f"{what}: index {counts.numel() - 1} out of range [0, {n_keys})")
-    start = torch.zeros(n_keys + 1, dtype=torch.int32, device=keys.device)
-    start[1:] = torch.cumsum(counts, 0)
-    return start, torch.sort(k, stable=True).indices.to(torch.int32)
+from ._call import call, csr, expect, ptr, upstream, wants_grad
 
 
 def _launch_face_frames(faces, v):
@@ -143,7 +131,7 @@ class _GaussianTable:
         tensor, ptr, version = key
         t = self._t
         if t is None or t[0] is not tensor or t[1:4] != (ptr, version, n_f):
-            self._t = t = (tensor, ptr, version, n_f) + _csr(binding, n_f, "binding")   # holds `tensor`: its address is not reused
+            self._t = t = (tensor, ptr, version, n_f) + csr(binding, n_f, "binding")   # holds `tensor`: its address is not reused
         return t[4], t[5]
 
 
@@ -156,7 +144,7 @@ class _VertexTable:
 
     def get(self, faces, n_v):
         if self._t is None or self._t[0] != n_v:
-            self._t = (n_v,) + _csr(faces, n_v, "faces")
+            self._t = (n_v,) + csr(faces, n_v, "faces")
         return self._t[1:]
 
 

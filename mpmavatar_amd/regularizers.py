@@ -26,8 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._call import call, expect, ptr, upstream, wants_grad
-from .mesh_frames import _csr
+from ._call import call, csr, expect, ptr, upstream, wants_grad
 
 K = 3             # MPMHIP_REG_K
 _TPB = 256        # MPMHIP_REG_TPB
@@ -147,7 +146,7 @@ class MeshRegularizer:
     def _vertex_table(self):
         if self._table is None:
             nbx = torch.cat([torch.arange(self.n_faces, dtype=torch.int32, device=self.faces.device)[:, None], self.face_neighbors], 1)
-            self._table = _csr(self.faces[nbx.long()], self.n_verts, "faces")       # S[f, s, c], item = 12 f + 3 s + c
+            self._table = csr(self.faces[nbx.long()], self.n_verts, "faces")       # S[f, s, c], item = 12 f + 3 s + c
         return self._table
 
     def terms(self, verts: torch.Tensor) -> torch.Tensor:

@@ -22,7 +22,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib as L
-from ._call import call, expect, ptr, upstream, wants_grad
+from ._call import call, csr, expect, ptr, upstream, wants_grad
 from .mesh_frames import _GaussianTable
 
 
@@ -38,9 +38,8 @@ def texel_table(uv, height, width):
     inside = (xs >= 0) & (xs <= W - 1) & (ys >= 0) & (ys <= H - 1)
     texel = (ys.clamp(0, H - 1).long() * width + xs.clamp(0, W - 1).long())[inside]     # row-major over (face, corner): ascending taps
     taps = torch.arange(4 * n_f, device=uv.device).reshape(n_f, 4)[inside]
-    start = torch.zeros(height * width + 1, dtype=torch.int32, device=uv.device)
-    start[1:] = torch.cumsum(torch.bincount(texel, minlength=height * width), 0)
-    return start, taps[torch.sort(texel, stable=True).indices].to(torch.int32).contiguous()
+    start, order = csr(texel, height * width, "texel")
+    return start, taps[order.long()].to(torch.int32).contiguous()
 
 
 class ShadowSampler:

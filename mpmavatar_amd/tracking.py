@@ -28,8 +28,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib as L
-from ._call import call, expect, ptr, upstream, wants_grad
-from .mesh_frames import _csr
+from ._call import call, csr, expect, ptr, upstream, wants_grad
 
 _TPB = 256        # MPMHIP_TRACK_TPB
 _MODES = {"distance": 0, "average": 1, "cubed": 2}     # MPMHIP_TRACK_DISTANCE, _AVERAGE, _CUBED
@@ -60,7 +59,7 @@ class _Mesh:
 
     def _table(self, n_verts):
         if self._table_key != n_verts:
-            self._table_key, self._table_value = n_verts, _csr(self.faces, n_verts, "faces")
+            self._table_key, self._table_value = n_verts, csr(self.faces, n_verts, "faces")
         return self._table_value
 
 

@@ -144,8 +144,42 @@ def host_binding_backward(n_f, binding, xyz, rot, scl, opa, mat, quat, fscale, g
     return outs + fouts
 
 
-def host_frames_forward(verts, faces):
-    """the forward's saved outputs in float32, as oracle/face_frames.py (pinned against the reference) states them"""
+# ---- the host build of frames_math.hpp: the forward itself (tests/hostframes/hostframes.cpp) -------------------------------------
+
+# the bounds tests/test_frames.py asserts for the device against tests/golden/frames.npz and oracle/face_frames.py
+FRAME_TOL = {"mat": 2e-6, "scale": 1e-6, "center": 5e-7, "quat": 5e-6}
+
+
+def frames_lib():
+    return hostbuild.host_lib("hostframes")
+
+
+def host_frames_forward(verts, faces, n_f=None):
+    """k_face_frames on the host -> (face_center [n_f, 3], face_orien_mat [n_f, 3, 3], face_orien_quat [n_f, 4] WXYZ, face_scaling
+    [n_f, 1]); n_f: only the first n_f faces (the outputs have that many rows)"""
+    verts, faces = _f32(verts), np.ascontiguousarray(faces, np.int32)
+    n_f = faces.shape[0] if n_f is None else n_f
+    new = lambda *s: np.full(s, np.nan, np.float32)
+    center, mat, quat, scale = new(n_f, 3), new(n_f, 3, 3), new(n_f, 4), new(n_f, 1)
+    frames_lib().hfr_face_frames(_p(verts), _p(faces), n_f, _p(center), _p(mat), _p(quat), _p(scale))
+    return center, mat, quat, scale
+
+
+def host_quat_from_pieces(mat):
+    """the matrix -> quaternion map as the backward states it (quat_branch, quat_numerators, norm4 of frames_math.hpp) on a saved
+    face_orien_mat -> (branch int32 [n_f], unit quaternion WXYZ [n_f, 4])"""
+    mat = _f32(mat)
+    branch, quat = np.full(mat.shape[0], -1, np.int32), np.full((mat.shape[0], 4), np.nan, np.float32)
+    frames_lib().hfr_quat_from_pieces(_p(mat), mat.shape[0], _p(branch), _p(quat))
+    return branch, quat
+
+
+def host_quat_branch(mat):
+    return host_quat_from_pieces(mat)[0]
+
+
+def oracle_frames(verts, faces):
+    """the same four arrays as oracle/face_frames.py (pinned against the reference) states them"""
     from oracle import face_frames as ff
     o = ff.MeshFramesOracle(np.asarray(faces))
     o.set_mesh_by_verts(np.asarray(verts))

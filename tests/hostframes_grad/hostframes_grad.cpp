@@ -2,7 +2,8 @@
 // (tests/test_binding_grad_host.py; the stand-in for <hip/hip_runtime.h> is tests/hostmath/stub): serial loops over the four per-item
 // functions, one loop per kernel of frames_backward.hip, with the same CSR indexing and the same order of the sums.
 // With -DHOSTFRAMES_GRAD_MAIN the file is a stand-alone program for a sanitizer build: it reads an index structure (faces, binding)
-// from a file, fills in synthetic values and runs every loop, also with n = 0.
+// from a file, fills in synthetic parameters, runs the per-face forward (frm::face_frame_row, the loop of tests/hostframes/) into
+// exactly sized outputs and every backward loop on what it saved, also with n = 0.
 #include "frames_grad_math.hpp"
 
 #include <cstdint>
@@ -57,12 +58,9 @@ int run(int n_v, const std::vector<int32_t> &faces, const std::vector<int32_t> &
     verts[3 * v + 1] = std::sin(1.3f * v);
     verts[3 * v + 2] = std::cos(2.1f * v + 1.f);
   }
-  std::vector<float> mat(9 * (size_t)n_f), quat(4 * (size_t)n_f), fscale(n_f);
-  for (int f = 0; f < n_f; ++f) {  // synthetic "saved" frames: any values serve an index check
-    for (int k = 0; k < 9; ++k) mat[9 * f + k] = synth(9 * f + k);
-    for (int k = 0; k < 4; ++k) quat[4 * f + k] = synth(4 * f + k + 1);
-    fscale[f] = 0.1f + 0.01f * (f % 7);
-  }
+  // the real forward into exactly sized outputs: a write past a row is the sanitizer's to report
+  std::vector<float> center(3 * (size_t)n_f), mat(9 * (size_t)n_f), quat(4 * (size_t)n_f), fscale(n_f);
+  for (int f = 0; f < n_f; ++f) frm::face_frame_row(f, verts.data(), faces.data(), center.data(), mat.data(), quat.data(), fscale.data());
   std::vector<float> xyz(3 * (size_t)n), rot(4 * (size_t)n), scl(3 * (size_t)n), opa(n), gm(3 * (size_t)n), gr(4 * (size_t)n), gs(3 * (size_t)n), go(n);
   for (int i = 0; i < 3 * n; ++i) { xyz[i] = synth(i); scl[i] = -1.f + synth(i + 5); gm[i] = synth(i + 11); gs[i] = synth(i + 13); }
   for (int i = 0; i < 4 * n; ++i) { rot[i] = synth(i + 3); gr[i] = synth(i + 17); }

@@ -142,6 +142,19 @@ def test_cases_meet_the_conditions(name):
 # ---- frames_grad_math.hpp on the host against the float64 twin ---------------------------------------------------------------------
 
 @pytest.mark.parametrize("name", bc.CASES)
+def test_host_forward_agrees_with_the_oracle(name):
+    """the saved frames the backward is fed come from the host build of the forward itself (frames_math.hpp); the oracle stays pinned
+    to it within the bounds the device is held to (bc.FRAME_TOL), and both take the same quaternion branch on every face"""
+    c = bc.case(name)
+    got, want = bc.host_frames_forward(c["verts"], c["faces"]), bc.oracle_frames(c["verts"], c["faces"])
+    for k, g, w in zip(("center", "mat", "quat", "scale"), got, want):
+        err = np.abs(g - w).max()
+        print(name, k, "%.3g of bound %.3g" % (err, bc.FRAME_TOL[k]))
+        assert g.shape == w.shape and err < bc.FRAME_TOL[k], k
+    assert np.array_equal(bc.host_quat_branch(got[1]), tw.quat_branch(torch.from_numpy(want[1]))[0].numpy())
+
+
+@pytest.mark.parametrize("name", bc.CASES)
 def test_host_gradients_against_float64(name):
     got, want = bc.host_grads(bc.case(name)), bc.g64(name)
     for k in bc.NAMES:

@@ -79,6 +79,96 @@ def rel_ok(a, b, tol=2e-6):
     return bool((np.abs(a - b) <= tol * np.abs(b) + 1e-12).all())
 
 
+# ---- the four forward kernels on small inputs, through the entry points --------------------------------------------------------------
+# The first 257 faces of frames.npz and its five degenerate ones (TPB is 256: one full workgroup and a partial one), and the first 257
+# Gaussians of render_inputs.npz on that fixture's own 198 faces, which their binding already lies in.  The inputs are a subset of the
+# ones the bounds of test_hip_frames_and_binding and test_render_inputs.TOL were set on, rows do not depend on one another, so the
+# bounds are those.  Keeping the Gaussians on their own mesh is what lets their rows be held to the fixture; the price is that
+# the render kernel is never run here on frames of the small face set of frames.npz (test_hip_frames_and_binding binds 4000
+# Gaussians to the whole of it).
+
+N_SMALL = 257
+
+
+def _small_mesh():
+    n = int(GOLD["n_regular"])
+    rows = np.r_[0:N_SMALL, n:GOLD["faces"].shape[0]]
+    return rows, np.ascontiguousarray(GOLD["faces"][rows])
+
+
+def _device_frames(verts, faces, n_f, rows=None):
+    """mpmhip_face_frames over the first n_f faces into NaN-filled outputs of `rows` rows -> (center, mat, quat, scale) as numpy"""
+    import torch
+    from mpmavatar_amd._call import call
+    dev = torch.device("cuda:0")
+    v, f = torch.from_numpy(np.ascontiguousarray(verts)).to(dev), torch.from_numpy(np.ascontiguousarray(faces, np.int32)).to(dev)
+    out = [torch.full((n_f if rows is None else rows, *s), float("nan"), device=dev) for s in ((3,), (3, 3), (4,), (1,))]
+    call("mpmhip_face_frames", dev, v.data_ptr(), f.data_ptr(), n_f, *[t.data_ptr() for t in out])
+    return [t.cpu().numpy() for t in out]
+
+
+def _device_render(n_g, n_x, rows=None):
+    """mpmhip_render_inputs over the first n_g Gaussians and the first n_x `extra` rows of render_inputs.npz, on that fixture's mesh,
+    into NaN-filled outputs of `rows` rows -> dict of numpy arrays"""
+    import torch
+    import test_render_inputs as tri
+    from mpmavatar_amd._call import call
+    R = tri.GOLD
+    dev = torch.device("cuda:0")
+    t = lambda a, dt=np.float32: torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev)
+    frames = [torch.from_numpy(a).to(dev) for a in _device_frames(R["verts"], R["faces"], R["faces"].shape[0])]
+    ins = [t(R["binding"], np.int32)] + [t(R[k]) for k in ("_xyz", "_rotation", "_scaling", "_opacity")]
+    ext = [t(R["extra_" + k]) for k in ("xyz", "opacity", "scales", "rotations")]
+    out = {k: torch.full((n_g + n_x if rows is None else rows, w), float("nan"), device=dev)
+           for k, w in (("means3D", 3), ("means2D", 3), ("opacities", 1), ("scales", 3), ("rotations", 4))}
+    call("mpmhip_render_inputs", dev, n_g, n_x, *[a.data_ptr() for a in ins], *[a.data_ptr() for a in frames], *[a.data_ptr() for a in ext],
+         *[a.data_ptr() for a in out.values()])
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+@pytest.mark.gpu
+def test_hip_small_frames_match_the_fixture_and_the_host_branch():
+    import torch
+    import binding_grad_cases as bc
+    import binding_twin_torch as tw
+    rows, faces = _small_mesh()
+    center, mat, quat, scl = _device_frames(GOLD["verts"], faces, faces.shape[0])
+    n = N_SMALL
+    assert np.abs(mat[:n] - GOLD["orientation"][rows][:n]).max() < 2e-6
+    assert np.abs(scl[:n] - GOLD["scale"][rows][:n]).max() < 1e-6 and np.abs(center - GOLD["center"][rows]).max() < 5e-7
+    assert np.isfinite(mat).all() and np.allclose(mat[n:], GOLD["orientation"][rows][n:], atol=1e-5)
+    o = ff.MeshFramesOracle(faces)
+    o.set_mesh_by_verts(GOLD["verts"])
+    assert np.abs(quat[:n] - o.face_orien_quat[:n]).max() < 5e-6
+    # the branch the device took, recovered from the matrix it saved, is the host build's on every regular face
+    host_mat = bc.host_frames_forward(GOLD["verts"], faces)[1]
+    assert np.array_equal(tw.quat_branch(torch.from_numpy(mat))[0].numpy()[:n], bc.host_quat_branch(host_mat)[:n])
+    for k in (1, 255, 256, 257):                                           # rows do not depend on the row count: bitwise
+        part = _device_frames(GOLD["verts"], faces, k)
+        for a, b in zip(part, (center, mat, quat, scl)):
+            assert np.array_equal(a, b[:k]), k
+    for a in _device_frames(GOLD["verts"], faces, 0, rows=2):              # nothing to do: OK, and nothing written
+        assert np.isnan(a).all()
+
+
+@pytest.mark.gpu
+def test_hip_small_render_inputs_match_the_fixture():
+    import test_render_inputs as tri
+    R, n = tri.GOLD, N_SMALL
+    whole = _device_render(n, 3)
+    for k in tri.KEYS:
+        assert tri._close(whole[k][:n], R[k][:n], tri.TOL[k]), k
+    for n_g, n_x in ((1, 0), (253, 3), (254, 3), (0, 3)):                  # 1, 256, 257 rows, and `extra` rows alone
+        part = _device_render(n_g, n_x, rows=n_g + n_x + 2)
+        for k, e in (("means3D", "xyz"), ("opacities", "opacity"), ("scales", "scales"), ("rotations", "rotations")):
+            assert np.array_equal(part[k][:n_g], whole[k][:n_g]), (k, n_g)
+            assert np.array_equal(part[k][n_g:n_g + n_x], R["extra_" + e][:n_x].reshape(n_x, part[k].shape[1])), (k, n_g)      # bitwise copies
+            assert np.isnan(part[k][n_g + n_x:]).all(), (k, n_g)
+        assert (part["means2D"][:n_g + n_x] == 0).all() and np.isnan(part["means2D"][n_g + n_x:]).all()
+    for a in _device_render(0, 0, rows=2).values():                       # nothing to do: OK, and nothing written
+        assert np.isnan(a).all()
+
+
 @pytest.mark.gpu
 def test_hip_frames_from_simulated_vertices():
     """The intended use: frames of the cloth faces straight from the solver's particle_x (no host copy), sized like the

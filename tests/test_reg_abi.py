@@ -47,6 +47,7 @@ def _args(name, p, **change):
 
 def test_the_library_was_built_from_reg_hip_and_the_header_declares_all_four(lib):
     assert "reg.hip" in hipbuild.SOURCES and "reg_math.hpp" in hipbuild.HEADERS
+    assert "frames_math.hpp" in hipbuild.HEADERS        # the shared 3-vector and the binding's forward: a change rebuilds the objects
     header = open(os.path.join(ROOT, "include", "mpmhip.h")).read()
     for n in MESH + GAUSS:
         assert hasattr(lib, n) and n in L.SIGNATURES and f"int {n}(" in header
