@@ -11,7 +11,11 @@ without its dataset, its SMPL-X forward and pytorch3d:
                losses['collision_l'] = collision_penalty(vertices[cloth_v_idx], smplx_v, smplx_vn)   -> mpmhip_track_collision_forward
                loss.backward(); optimizer.step()                                   (FusedAdam, initialize_optimizer's groups :182-193)
 
-    python examples/tracking_step_demo.py [--steps 30] [--size 64]
+    python examples/tracking_step_demo.py [--steps 30] [--size 64] [--cloth-mask]
+
+``--cloth-mask`` adds the 4D-DRESS script's garment term (preprocess/train_mesh_lbs_4ddress.py:260-277, :299, :306): a synthetic
+two-garment labelling of the faces (upper: face centre above the equator, lower: below) goes in as ``extra_attrs``, the rasteriser's
+sixth slot is the rendered garment mask, and ``losses['cloth_mask'] = l1_loss(cloth_mask, gt_cloth_mask)`` enters with weight 2.
 
 The mesh is a 320-face icosphere of radius 0.5 with one Gaussian per face and a smaller sphere inside as the body, its vertex normals
 from ``VertexNormals``.  The ground-truth image and mask are rendered from a displaced copy of the mesh with other colours; Adam then
@@ -35,14 +39,14 @@ from mpmavatar_amd.tracking import FaceGaussians, VertexNormals, collision_penal
 
 # loss_weights of get_loss (:287-291) with the argparse defaults (:545-553)
 WEIGHTS = {"im": 1.0, "msk": 1.0, "scale": 1.0, "normal": 0.1, "opacity": 0.05, "iso": 20.0, "area": 50.0, "eq_faces_weight": 1000.0,
-           "collision_l": 10.0}
+           "collision_l": 10.0, "cloth_mask": 2.0}               # cloth_mask: train_mesh_lbs_4ddress.py:306, the 4D-DRESS script alone
 LR_MEANS3D, LR_COLORS = 0.00004, 0.0025                  # --lr_means3D, --lr_colors
 
 
 class Scene:
     """Everything one tracking step needs; ``params`` are the six leaves of the reference's ``params`` dict."""
 
-    def __init__(self, size=64, device="cuda:0", seed=0, eye=(0.0, 0.3, -2.0)):
+    def __init__(self, size=64, device="cuda:0", seed=0, eye=(0.0, 0.3, -2.0), cloth_mask=False):
         dev = torch.device(device)
         g = torch.Generator(device="cpu").manual_seed(seed)
         rnd = lambda *s: torch.randn(*s, generator=g)
@@ -66,12 +70,15 @@ class Scene:
         log_scales[:, :2] = 0.5 * torch.log(self.fg.face_areas(verts0) / torch.pi)[:, None]
         centre = verts0[self.faces.long()].mean(1)
         colour = (0.5 + centre / (2 * centre.norm(dim=1, keepdim=True))).contiguous()                 # colour by direction
+        # variables['cloth_mask'] of the 4D-DRESS script: [F, 2], upper and lower garment, 0 / 1 (data, not trained)
+        upper = (centre[:, 1] > 0).float()
+        self.cloth_table = torch.stack([upper, 1 - upper], 1).contiguous() if cloth_mask else None
         # the ground truth: a displaced copy (2 % larger, 0.004 of noise) with shifted colours and a camera gain
         with torch.no_grad():
             self.params = {"vertices": (1.02 * verts0 + 0.004 * rnd(*verts0.shape).to(dev)).contiguous(),
                            "rgb_colors": (colour + 0.1 * rnd(n_f, 3).to(dev)).clamp(0, 1).contiguous(), "logit_opacities": torch.full((n_f, 1), 3.0, device=dev),
                            "log_scales": log_scales, "cam_m": torch.full((1, 3), 0.05, device=dev), "cam_c": torch.full((1, 3), 0.02, device=dev)}
-            self.gt_im, self.gt_msk, _ = self.render()
+            self.gt_im, self.gt_msk, _, self.gt_cloth_mask = self.render()
         self.params = {"vertices": verts0.clone(), "rgb_colors": colour, "logit_opacities": torch.zeros(n_f, 1, device=dev),
                        "log_scales": log_scales.clone(), "cam_m": torch.zeros(1, 3, device=dev), "cam_c": torch.zeros(1, 3, device=dev)}
         self.params = {k: torch.nn.Parameter(v.contiguous()) for k, v in self.params.items()}
@@ -80,19 +87,21 @@ class Scene:
         self.losses = {}
 
     def render(self, curr_id=0):
-        """-> (im [3, size, size] behind the camera affine, msk [1, size, size], radius [F])"""
+        """-> (im [3, size, size] behind the camera affine, msk [1, size, size], radius [F], cloth_mask [2, size, size] or None)"""
         p = self.params
-        rendervar = self.fg.render_vars(p["vertices"], p["log_scales"], p["logit_opacities"])
+        rendervar = self.fg.render_vars(p["vertices"], p["log_scales"], p["logit_opacities"], extra_attrs=self.cloth_table)
         rendervar["colors_precomp"] = p["rgb_colors"]
         rendervar["means2D"] = torch.zeros_like(rendervar["means3D"], requires_grad=True)
-        im, _, _, msk, radius, _ = GaussianRasterizer(raster_settings=self.cam)(**rendervar)
+        im, _, _, msk, radius, cloth_mask = GaussianRasterizer(raster_settings=self.cam)(**rendervar)
         im = torch.exp(p["cam_m"][curr_id])[:, None, None] * im + p["cam_c"][curr_id][:, None, None]
-        return im, msk, radius
+        return im, msk, radius, cloth_mask
 
     def loss(self):
         p = self.params
-        im, msk, radius = self.render()
+        im, msk, radius, cloth_mask = self.render()
         losses = {"im": image_loss(im, self.gt_im, 0.2)[0], "msk": l1_loss(msk, self.gt_msk)}
+        if cloth_mask is not None:
+            losses["cloth_mask"] = l1_loss(cloth_mask, self.gt_cloth_mask)       # :306
         losses["area"], losses["scale"], losses["opacity"] = self.fg.losses(p["vertices"], p["log_scales"], p["logit_opacities"])
         losses["normal"], losses["iso"], losses["eq_faces_weight"] = self.reg(p["vertices"])
         losses["collision_l"] = collision_penalty(p["vertices"][self.cloth_v_idx], self.smplx_v, self.smplx_vn, return_average=True)
@@ -104,8 +113,9 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--size", type=int, default=64)
+    ap.add_argument("--cloth-mask", action="store_true")
     a = ap.parse_args(argv)
-    sc = Scene(a.size)
+    sc = Scene(a.size, cloth_mask=a.cloth_mask)
     opt = FusedAdam([{"params": [v], "name": k, "lr": sc.lrs[k]} for k, v in sc.params.items()], lr=0.0, eps=1e-15)
     losses = []
     for step in range(a.steps + 1):

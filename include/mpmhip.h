@@ -748,6 +748,35 @@ int mpmhip_raster_backward(mpmhip_raster *r, const mpmhip_raster_settings *s, in
                            int64_t n_entries, const float *dL_dimage, const float *dL_dalpha, float *d_means3D, float *d_means2D,
                            float *d_shs, float *d_colors_precomp, float *d_opacities, float *d_scales, float *d_rotations,
                            float *d_cov3D_precomp);
+/* ---- extra attribute channels: what the 4D-DRESS tracking script needs of the render call -----------------------------------
+ * preprocess/train_mesh_lbs_4ddress.py:260-277 hands the rasteriser 'extra_attrs': variables['cloth_mask'], an [N, 2] table
+ * (upper and lower garment, 0 / 1), :299 reads the blended channels back as the sixth value of the call, and :306 compares them
+ * with the data's garment mask (l1_loss_v1, weight 2).  Per pixel, with alpha_k, T_k and the finishing rule of the colour,
+ *   extra_e = sum_k a_ke alpha_k T_k,  e = 0 .. E-1,  1 <= E <= 8,  no background term
+ * (UNCONFIRMED against the CUDA original, whose source is not at hand: DESIGN.md).  The gradient is the exact derivative with the
+ * decisions held fixed, as above; the extras' share of the geometry and opacity gradients adds to that of image and alpha.
+ *
+ *   mpmhip_raster_extra_forward   train_mesh_lbs_4ddress.py:260-277, :299 (what :306 then compares).  One more walk over the tile lists of the frame that
+ *                                 mpmhip_raster_forward_grad has just rendered on this handle, each pixel up to where its colour
+ *                                 walk stopped: extra [dev] [n*E] -> out_extra [dev] [E*H*W], every element written (zeros where
+ *                                 nothing contributes, and for n == 0).  Valid only directly after a forward_grad of the same n
+ *                                 and image size on the handle: MPMHIP_ERR_STATE otherwise.  Asynchronous on the handle's stream.
+ *   mpmhip_raster_backward_extra  train_mesh_lbs_4ddress.py:306 and its loss.backward(), back through the call of :299 to the
+ *                                 table of :260-277.  mpmhip_raster_backward (same arguments,
+ *                                 same stages) with the extras' tile pass in between: extra [n*E] as in the forward call, g_extra
+ *                                 [E*H*W] = dL/dextra (NULL = zeros), d_extra [n*E] = dL/dextra_attrs, every element written.
+ *                                 Its temporaries (the 36 B per entry of mpmhip_raster_backward and 4 E more) live in the handle.
+ * MPMHIP_ERR_INVALID and nothing launched: E < 1 or E > 8, a NULL extra, out_extra or d_extra (n > 0), and the conditions of
+ * mpmhip_raster_backward. */
+int mpmhip_raster_extra_forward(mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, const float *extra, int32_t E,
+                                float *out_extra);
+int mpmhip_raster_backward_extra(mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, const float *means3D, const float *shs,
+                                 int32_t n_sh_coeffs, const float *colors_precomp, const float *opacities, const float *scales,
+                                 const float *rotations, const float *cov3D_precomp, const void *saved, int64_t saved_bytes,
+                                 int64_t n_entries, const float *dL_dimage, const float *dL_dalpha, float *d_means3D,
+                                 float *d_means2D, float *d_shs, float *d_colors_precomp, float *d_opacities, float *d_scales,
+                                 float *d_rotations, float *d_cov3D_precomp, const float *extra, int32_t E, const float *g_extra,
+                                 float *d_extra);
 /* counts of the newest frame; synchronous, runs one small count kernel */
 int mpmhip_raster_stats(const mpmhip_raster *r, mpmhip_raster_stats_t *out);
 /* Measurement only (tools/raster_bench.py; the counterpart of mpmhip_profile_enable for this pipeline): while on, every

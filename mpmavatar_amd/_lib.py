@@ -154,6 +154,10 @@ SIGNATURES = {
     "mpmhip_raster_saved_bytes": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mpmhip_raster_save": (C.c_int, [vp, vp, C.c_int64]),
     "mpmhip_raster_backward": (C.c_int, [vp, C.POINTER(RasterSettings), C.c_int32, vp, vp, C.c_int32] + [vp] * 6 + [C.c_int64, C.c_int64] + [vp] * 10),
+    # extra attribute channels: preprocess/train_mesh_lbs_4ddress.py:260-277 (the table), :299 (the sixth slot), :306 (its loss)
+    "mpmhip_raster_extra_forward": (C.c_int, [vp, C.POINTER(RasterSettings), C.c_int32, vp, C.c_int32, vp]),
+    "mpmhip_raster_backward_extra": (C.c_int, [vp, C.POINTER(RasterSettings), C.c_int32, vp, vp, C.c_int32] + [vp] * 6 + [C.c_int64, C.c_int64] + [vp] * 10
+                                     + [vp, C.c_int32, vp, vp]),
     "mpmhip_raster_stats": (C.c_int, [vp, C.POINTER(RasterStats)]),
     "mpmhip_raster_profile": (C.c_int, [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "mpmhip_image_loss_forward": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]),

@@ -233,7 +233,7 @@ void mpmhip_raster_destroy(mpmhip_raster *r) {
   (void)hipSetDevice(r->device);
   (void)hipStreamSynchronize(r->stream);
   void *dev[] = {r->rec0, r->rec1, r->colour, r->rect, r->touched, r->offsets, r->scan_tmp, r->keys[0], r->keys[1],
-                 r->vals[0], r->vals[1], r->sort_tmp, r->ranges, r->d_counts, r->pix_T, r->pix_stop, r->inv, r->rows};
+                 r->vals[0], r->vals[1], r->sort_tmp, r->ranges, r->d_counts, r->pix_T, r->pix_stop, r->inv, r->rows, r->xrows};
   for (void *p : dev)
     if (p) (void)hipFree(p);
   if (r->h_total) (void)hipHostFree(r->h_total);
@@ -365,6 +365,7 @@ int forward_impl(mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, c
                        s->bg[0], s->bg[1], s->bg[2], out_color, out_alpha, r->pix_T, r->pix_stop);
     r->grad_frame = true;
     r->grad_n = n; r->grad_tiles = tiles; r->grad_pixels = (size_t)W * H; r->grad_entries = (int64_t)total;
+    r->grad_w = W; r->grad_h = H;
   } else {
     hipLaunchKernelGGL(k_raster_render<false>, dim3((unsigned)gx, (unsigned)gy), TPB, 0, st, W, H, gx, (const uint2 *)r->ranges,
                        (const uint32_t *)r->vals[1], (const float4 *)r->rec0, (const float4 *)r->rec1, (const float *)r->colour,
@@ -423,7 +424,7 @@ int mpmhip_raster_stats(const mpmhip_raster *r, mpmhip_raster_stats_t *out) {
                                  ((size_t)r->cap_n + 1) * (sizeof(uint32_t) + sizeof(uint64_t)) + r->scan_tmp_bytes +
                                  r->cap_e * 2 * (sizeof(uint64_t) + sizeof(uint32_t)) + r->sort_tmp_bytes +
                                  (size_t)r->cap_tiles * sizeof(uint2) + r->cap_pix * (sizeof(float) + sizeof(uint32_t)) +
-                                 r->cap_inv * sizeof(uint32_t) + r->cap_rows * sizeof(float));
+                                 r->cap_inv * sizeof(uint32_t) + (r->cap_rows + r->cap_xrows) * sizeof(float));
   return MPMHIP_OK;
 }
 

@@ -104,10 +104,6 @@ __global__ __launch_bounds__(TPB) void k_raster_backward_tiles(int W, int H, int
   }
 }
 
-struct Grads {
-  float *means, *means2d, *shs, *colors, *opac, *scales, *rots, *cov;
-};
-
 // One lane per Gaussian.  Every output element of the Gaussian is written: zeros when it was culled.
 __global__ __launch_bounds__(TPB) void k_raster_backward_gaussians(int n, Camera cam, Inputs in, const int4 *__restrict__ rect,
                                                                    const uint64_t *__restrict__ offsets,
@@ -184,43 +180,65 @@ int reserve_rows(mpmhip_raster *r, size_t count) {
 
 }  // namespace
 
+namespace raster_host {
+
+int backward_check(const mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, const Inputs &in, const void *saved,
+                   int64_t saved_bytes, int64_t n_entries, const Grads &out, BackwardFrame *frame) {
+  if (!saved || n_entries < 0 || n_entries > (int64_t)INT32_MAX) return MPMHIP_ERR_INVALID;
+  if (n > 0) {
+    if (!out.means || !out.means2d || !out.opac) return MPMHIP_ERR_INVALID;
+    if (in.shs ? !out.shs : !out.colors) return MPMHIP_ERR_INVALID;
+    if (in.scales && in.rots ? (!out.scales || !out.rots) : !out.cov) return MPMHIP_ERR_INVALID;
+  } else if (n_entries != 0) {
+    return MPMHIP_ERR_INVALID;
+  }
+  int gx = 0, gy = 0;
+  if (int rc = validate_frame(r, s, n, in, &gx, &gy)) return rc;
+  const int W = s->image_width, H = s->image_height;
+  *frame = BackwardFrame{W, H, gx, gy, saved_layout((size_t)n, (size_t)gx * gy, (size_t)W * H, (size_t)n_entries)};
+  if (saved_bytes != (int64_t)frame->l.bytes) return MPMHIP_ERR_INVALID;  // another n, image size or entry count than the frame's
+  return MPMHIP_OK;
+}
+
+int backward_tiles(mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, const BackwardFrame &f, const void *saved,
+                   int64_t n_entries, const float *dL_dimage, const float *dL_dalpha) {
+  if (n_entries <= 0) return MPMHIP_OK;
+  const SavedLayout &l = f.l;
+  const char *sv = (const char *)saved;
+  if (int rc = reserve_rows(r, (size_t)n_entries * NP)) return rc;
+  hipLaunchKernelGGL(k_raster_backward_tiles, dim3((unsigned)f.gx, (unsigned)f.gy), TPB, 0, r->stream, f.W, f.H, f.gx,
+                     (uint32_t)n_entries, (uint32_t)n, (const uint2 *)(sv + l.ranges), (const uint32_t *)(sv + l.vals),
+                     (const float4 *)(sv + l.rec0), (const float4 *)(sv + l.rec1), (const float *)(sv + l.colour),
+                     (const float *)(sv + l.pix_T), (const uint32_t *)(sv + l.pix_stop), s->bg[0], s->bg[1], s->bg[2], dL_dimage,
+                     dL_dalpha, r->rows);
+  return check(hipGetLastError());
+}
+
+int backward_gaussians(mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, const Inputs &in, const BackwardFrame &f,
+                       const void *saved, int64_t n_entries, const Grads &out) {
+  const SavedLayout &l = f.l;
+  const char *sv = (const char *)saved;
+  Camera cam{f.W, f.H, f.gx, f.gy, s->tanfovx, s->tanfovy, s->scale_modifier, s->sh_degree, s->viewmatrix, s->projmatrix, s->campos};
+  hipLaunchKernelGGL(k_raster_backward_gaussians, blocks(n, TPB), TPB, 0, r->stream, n, cam, in, (const int4 *)(sv + l.rect),
+                     (const uint64_t *)(sv + l.offsets), (const uint32_t *)(sv + l.inv), (uint32_t)n_entries,
+                     (const float *)r->rows, out);
+  return check(hipGetLastError());
+}
+
+}  // namespace raster_host
+
 extern "C" int mpmhip_raster_backward(mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, const float *means3D,
                                       const float *shs, int32_t n_sh_coeffs, const float *colors_precomp, const float *opacities,
                                       const float *scales, const float *rotations, const float *cov3D_precomp, const void *saved,
                                       int64_t saved_bytes, int64_t n_entries, const float *dL_dimage, const float *dL_dalpha,
                                       float *d_means3D, float *d_means2D, float *d_shs, float *d_colors_precomp, float *d_opacities,
                                       float *d_scales, float *d_rotations, float *d_cov3D_precomp) {
-  if (!saved || n_entries < 0 || n_entries > (int64_t)INT32_MAX) return MPMHIP_ERR_INVALID;
-  if (n > 0) {
-    if (!d_means3D || !d_means2D || !d_opacities) return MPMHIP_ERR_INVALID;
-    if (shs ? !d_shs : !d_colors_precomp) return MPMHIP_ERR_INVALID;
-    if (scales && rotations ? (!d_scales || !d_rotations) : !d_cov3D_precomp) return MPMHIP_ERR_INVALID;
-  } else if (n_entries != 0) {
-    return MPMHIP_ERR_INVALID;
-  }
   const Inputs in{means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, n_sh_coeffs};
-  int gx = 0, gy = 0;
-  if (int rc = validate_frame(r, s, n, in, &gx, &gy)) return rc;
-  const int W = s->image_width, H = s->image_height, tiles = gx * gy;
-  const SavedLayout l = saved_layout((size_t)n, (size_t)tiles, (size_t)W * H, (size_t)n_entries);
-  if (saved_bytes != (int64_t)l.bytes) return MPMHIP_ERR_INVALID;  // another n, image size or entry count than the frame's
-  if (n == 0) return MPMHIP_OK;                                     // nothing to write
+  const Grads out{d_means3D, d_means2D, d_shs, d_colors_precomp, d_opacities, d_scales, d_rotations, d_cov3D_precomp};
+  BackwardFrame f;
+  if (int rc = backward_check(r, s, n, in, saved, saved_bytes, n_entries, out, &f)) return rc;
+  if (n == 0) return MPMHIP_OK;  // nothing to write
   ENTRY_CHECK(hipSetDevice(r->device));
-  hipStream_t st = r->stream;
-  const char *sv = (const char *)saved;
-  if (n_entries > 0) {
-    if (int rc = reserve_rows(r, (size_t)n_entries * NP)) return rc;
-    hipLaunchKernelGGL(k_raster_backward_tiles, dim3((unsigned)gx, (unsigned)gy), TPB, 0, st, W, H, gx, (uint32_t)n_entries,
-                       (uint32_t)n, (const uint2 *)(sv + l.ranges), (const uint32_t *)(sv + l.vals), (const float4 *)(sv + l.rec0),
-                       (const float4 *)(sv + l.rec1), (const float *)(sv + l.colour), (const float *)(sv + l.pix_T),
-                       (const uint32_t *)(sv + l.pix_stop), s->bg[0], s->bg[1], s->bg[2], dL_dimage, dL_dalpha, r->rows);
-    ENTRY_CHECK(hipGetLastError());
-  }
-  Camera cam{W, H, gx, gy, s->tanfovx, s->tanfovy, s->scale_modifier, s->sh_degree, s->viewmatrix, s->projmatrix, s->campos};
-  Grads out{d_means3D, d_means2D, d_shs, d_colors_precomp, d_opacities, d_scales, d_rotations, d_cov3D_precomp};
-  hipLaunchKernelGGL(k_raster_backward_gaussians, blocks(n, TPB), TPB, 0, st, n, cam, in, (const int4 *)(sv + l.rect),
-                     (const uint64_t *)(sv + l.offsets), (const uint32_t *)(sv + l.inv), (uint32_t)n_entries,
-                     (const float *)r->rows, out);
-  ENTRY_CHECK(hipGetLastError());
-  return MPMHIP_OK;
+  if (int rc = backward_tiles(r, s, n, f, saved, n_entries, dL_dimage, dL_dalpha)) return rc;
+  return backward_gaussians(r, s, n, in, f, saved, n_entries, out);
 }

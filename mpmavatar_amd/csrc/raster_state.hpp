@@ -47,6 +47,10 @@ struct mpmhip_raster {
   int64_t grad_entries = 0;
   size_t cap_rows = 0;
   float *rows = nullptr;         // the backward pass's own temporary: [entries][N_PARTIALS]
+  // Extra attribute channels (raster_extra.hip); nothing here is allocated before the first backward pass with extras.
+  int grad_w = 0, grad_h = 0;    // image size of the newest forward_grad frame: mpmhip_raster_extra_forward asks for the same
+  size_t cap_xrows = 0;
+  float *xrows = nullptr;        // the attribute partials of that backward pass: [entries][E]
   // mpmhip_raster_profile: events between the stages of a frame (off by default: no events, no extra synchronisation)
   bool profile = false;
   hipEvent_t ev[MPMHIP_RASTER_STAGES + 1] = {};
@@ -114,6 +118,27 @@ inline int validate_frame(const mpmhip_raster *r, const mpmhip_raster_settings *
   if ((int64_t)*gx * *gy > INT32_MAX || *gy > 65535) return MPMHIP_ERR_LIMIT;
   return MPMHIP_OK;
 }
+
+struct Grads {  // the outputs of the backward call; the alternatives that the frame does not use are NULL
+  float *means, *means2d, *shs, *colors, *opac, *scales, *rots, *cov;
+};
+
+// mpmhip_raster_backward in its stages (raster_backward.hip), so that mpmhip_raster_backward_extra (raster_extra.hip) runs the
+// very same ones with its own tile pass in between:
+//   backward_check      every condition of the call (MPMHIP_ERR_INVALID / _LIMIT); launches nothing.  *frame = the image
+//                       size, the tile grid and the layout of `saved`
+//   backward_tiles      the row buffer of the frame's entries and k_raster_backward_tiles over it (n_entries > 0)
+//   backward_gaussians  k_raster_backward_gaussians over the rows (n > 0)
+struct BackwardFrame {
+  int W, H, gx, gy;
+  SavedLayout l;
+};
+int backward_check(const mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, const Inputs &in, const void *saved,
+                   int64_t saved_bytes, int64_t n_entries, const Grads &out, BackwardFrame *frame);
+int backward_tiles(mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, const BackwardFrame &f, const void *saved,
+                   int64_t n_entries, const float *dL_dimage, const float *dL_dalpha);
+int backward_gaussians(mpmhip_raster *r, const mpmhip_raster_settings *s, int32_t n, const Inputs &in, const BackwardFrame &f,
+                       const void *saved, int64_t n_entries, const Grads &out);
 
 template <class T>
 inline int regrow(T *&p, size_t count) {

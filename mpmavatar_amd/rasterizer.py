@@ -35,6 +35,17 @@ per-pixel T and stopping position) in a tensor held by the autograd node: the sc
 device and stream, and the next forward overwrites it.  What is NOT differentiable: ``BoundGaussians.render_inputs`` is a
 forward-only launch, so gradients stop at its outputs; densification itself is the caller's.
 
+EXTRA ATTRIBUTE CHANNELS.  ``extra_attrs`` [N, E] (contiguous float32 on the same device, 1 <= E <= 8) is the table the 4D-DRESS
+tracking script hands over (preprocess/train_mesh_lbs_4ddress.py:260-277: ``variables['cloth_mask']``, upper and lower garment); the
+sixth value of the result is then [E, H, W], ``extra_e = sum_k a_ke alpha_k T_k`` with the alpha, T and finishing rule of the colour
+and NO background term (:299 reads it, :306 compares it with the data's garment mask).  UNCONFIRMED against the CUDA original, whose
+source is not at hand.  It is one more walk over the tile lists that the colour pass has sorted (``csrc/raster_extra.hip``), up to
+where each pixel's colour walk stopped, so such a frame always runs the training flavour of the colour pass; its state is saved only
+when a graph is built.  A graph is built when ``extra_attrs`` or any input other than ``means2D`` requires grad; the extras' share
+of the geometry and opacity gradients adds to that of image and alpha, and the table gets ``dL/da_ke = g_e alpha_k T_k``.  When slot
+5 is not used by the loss its gradient arrives as None and the backward pass is exactly that of a call without extras, bit for bit.
+Without ``extra_attrs`` nothing changes: the same kernels and entry points, ``None`` in slot 5.
+
 Each call blocks the host once (the pipeline reads one count back to size its sort, csrc/raster.hip).  The three floats of
 ``bg`` are read from the device the first time a given tensor is seen and kept until it is modified in place or freed, so
 a loop that renders against one background tensor, as the reference's does, adds no second wait.  No CPU fallback: tensors
@@ -83,6 +94,7 @@ class _Handle:
         weakref.finalize(self, self.lib.mpmhip_raster_destroy, self.ptr)
 
 
+MAX_EXTRA_ATTRS = 8   # channels of extra_attrs in one call (rast::EXTRA_MAX of csrc/raster_extra_math.hpp)
 _SHARED = {}
 _BG = {}    # id(bg tensor) -> (weak reference, version counter, three floats)
 
@@ -143,6 +155,50 @@ def _launch_forward(hd, cs, n, n_sh, tensors, grad):
     return image, alpha, radii
 
 
+def _launch_extra(hd, cs, n, extra):
+    """The extras of the frame that _launch_forward(..., grad=True) has just rendered on ``hd``: mpmhip_raster_extra_forward
+    -> [E, H, W].  It reads the frame's sorted lists and stopping positions out of the handle, so nothing may render in between."""
+    out = torch.empty(extra.shape[1], cs.image_height, cs.image_width, dtype=torch.float32, device=extra.device)
+    call_handle("mpmhip_raster_extra_forward", hd.ptr, C.byref(cs), n, _ptr(extra), extra.shape[1], out.data_ptr())
+    return out
+
+
+def _save_frame(fr, dev):
+    """copy the state of the handle's newest frame into a tensor that ``fr`` owns"""
+    size, entries = C.c_int64(), C.c_int64()
+    call_handle("mpmhip_raster_saved_bytes", fr.hd.ptr, C.byref(size), C.byref(entries))
+    fr.saved = torch.empty(size.value, dtype=torch.uint8, device=dev)
+    fr.n_entries = entries.value
+    call_handle("mpmhip_raster_save", fr.hd.ptr, fr.saved.data_ptr(), size.value)
+
+
+def _launch_backward(ctx, g_image, g_alpha, extra=None, g_extra=None):
+    """mpmhip_raster_backward over the frame of ``ctx``, or with ``g_extra`` mpmhip_raster_backward_extra -> the gradients in the
+    order of the autograd inputs behind ``fr``, and d_extra (None without ``g_extra``)"""
+    fr = ctx.fr
+    means3D, opacities, shs, colors_precomp, scales, rotations, cov3Ds_precomp = ctx.saved_tensors[:7]
+    hd, dev, n = fr.hd, means3D.device, fr.n
+    g_image, g_alpha = upstream(g_image, (3, fr.h, fr.w)), upstream(g_alpha, (1, fr.h, fr.w))
+    like = lambda t: None if t is None else torch.empty_like(t)
+    d_means3D, d_means2D, d_opac = torch.empty_like(means3D), torch.empty(n, 3, dtype=torch.float32, device=dev), torch.empty_like(opacities)
+    d_shs, d_col, d_scales, d_rots, d_cov = like(shs), like(colors_precomp), like(scales), like(rotations), like(cov3Ds_precomp)
+    p = _ptr
+    args = (hd.ptr, C.byref(fr.cs), n, p(means3D), p(shs), fr.n_sh, p(colors_precomp), p(opacities), p(scales), p(rotations),
+            p(cov3Ds_precomp), fr.saved.data_ptr(), fr.saved.numel(), fr.n_entries, p(g_image), p(g_alpha), p(d_means3D), p(d_means2D),
+            p(d_shs), p(d_col), p(d_opac), p(d_scales), p(d_rots), p(d_cov))
+    d_extra = None
+    if g_extra is None:
+        call_handle("mpmhip_raster_backward", *args)
+    else:
+        g_extra, d_extra = upstream(g_extra, (extra.shape[1], fr.h, fr.w)), torch.empty_like(extra)
+        call_handle("mpmhip_raster_backward_extra", *args, p(extra), extra.shape[1], p(g_extra), p(d_extra))
+    if ctx.means2D_shape is None or not ctx.needs_input_grad[2]:
+        d_means2D = None
+    elif ctx.means2D_shape != (n, 3):
+        raise RuntimeError(f"means2D: expected shape {(n, 3)} to receive its gradient, got {ctx.means2D_shape}")
+    return (None, d_means3D, d_means2D, d_opac, d_shs, d_col, d_scales, d_rots, d_cov), d_extra
+
+
 class _Rasterize(torch.autograd.Function):
     """forward: mpmhip_raster_forward_grad + mpmhip_raster_save; backward: mpmhip_raster_backward"""
 
@@ -150,11 +206,7 @@ class _Rasterize(torch.autograd.Function):
     def forward(ctx, fr, means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3Ds_precomp):
         hd, tensors = fr.hd, (means3D, shs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
         image, alpha, radii = _launch_forward(hd, fr.cs, fr.n, fr.n_sh, tensors, True)
-        size, entries = C.c_int64(), C.c_int64()
-        call_handle("mpmhip_raster_saved_bytes", hd.ptr, C.byref(size), C.byref(entries))
-        fr.saved = torch.empty(size.value, dtype=torch.uint8, device=means3D.device)
-        fr.n_entries = entries.value
-        call_handle("mpmhip_raster_save", hd.ptr, fr.saved.data_ptr(), size.value)
+        _save_frame(fr, means3D.device)
         ctx.fr = fr
         ctx.means2D_shape = None if means2D is None else tuple(means2D.shape)
         ctx.save_for_backward(means3D, opacities, shs, colors_precomp, scales, rotations, cov3Ds_precomp)
@@ -165,29 +217,39 @@ class _Rasterize(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_image, g_alpha, _g_radii):
-        fr = ctx.fr
-        means3D, opacities, shs, colors_precomp, scales, rotations, cov3Ds_precomp = ctx.saved_tensors
-        hd, dev, n = fr.hd, means3D.device, fr.n
-        g_image, g_alpha = upstream(g_image, (3, fr.h, fr.w)), upstream(g_alpha, (1, fr.h, fr.w))
-        like = lambda t: None if t is None else torch.empty_like(t)
-        d_means3D, d_means2D, d_opac = torch.empty_like(means3D), torch.empty(n, 3, dtype=torch.float32, device=dev), torch.empty_like(opacities)
-        d_shs, d_col, d_scales, d_rots, d_cov = like(shs), like(colors_precomp), like(scales), like(rotations), like(cov3Ds_precomp)
-        p = _ptr
-        call_handle("mpmhip_raster_backward", hd.ptr, C.byref(fr.cs), n, p(means3D), p(shs), fr.n_sh, p(colors_precomp), p(opacities),
-                    p(scales), p(rotations), p(cov3Ds_precomp), fr.saved.data_ptr(), fr.saved.numel(), fr.n_entries, p(g_image),
-                    p(g_alpha), p(d_means3D), p(d_means2D), p(d_shs), p(d_col), p(d_opac), p(d_scales), p(d_rots), p(d_cov))
-        if ctx.means2D_shape is None or not ctx.needs_input_grad[2]:
-            d_means2D = None
-        elif ctx.means2D_shape != (n, 3):
-            raise RuntimeError(f"means2D: expected shape {(n, 3)} to receive its gradient, got {ctx.means2D_shape}")
-        return None, d_means3D, d_means2D, d_opac, d_shs, d_col, d_scales, d_rots, d_cov
+        return _launch_backward(ctx, g_image, g_alpha)[0]
+
+
+class _RasterizeExtra(torch.autograd.Function):
+    """_Rasterize with ``extra_attrs``: forward adds mpmhip_raster_extra_forward between the render and the save; backward is
+    mpmhip_raster_backward_extra, or, when the extras' gradient arrives as None (slot 5 unused), exactly _Rasterize's."""
+
+    @staticmethod
+    def forward(ctx, fr, means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3Ds_precomp, extra_attrs):
+        hd, tensors = fr.hd, (means3D, shs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+        image, alpha, radii = _launch_forward(hd, fr.cs, fr.n, fr.n_sh, tensors, True)
+        extra = _launch_extra(hd, fr.cs, fr.n, extra_attrs)
+        _save_frame(fr, means3D.device)
+        ctx.fr = fr
+        ctx.means2D_shape = None if means2D is None else tuple(means2D.shape)
+        ctx.save_for_backward(means3D, opacities, shs, colors_precomp, scales, rotations, cov3Ds_precomp, extra_attrs)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)
+        return image, alpha, radii, extra
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_image, g_alpha, _g_radii, g_extra):
+        grads, d_extra = _launch_backward(ctx, g_image, g_alpha, ctx.saved_tensors[7], g_extra)
+        return grads + (d_extra,)
 
 
 class GaussianRasterizer:
     """``GaussianRasterizer(raster_settings)(means3D=, means2D=, shs=, colors_precomp=, opacities=, scales=, rotations=,
-    cov3Ds_precomp=)`` -> ``(image [3, H, W], None, None, alpha [1, H, W], radii [N] int32, None)``: the 6-tuple of the
-    reference's call, of which it reads slots 0, 3 and 4 (gaussian_renderer/__init__.py:95).  image and alpha carry a graph when
-    an input other than means2D requires grad (module docstring)."""
+    cov3Ds_precomp=, extra_attrs=)`` -> ``(image [3, H, W], None, None, alpha [1, H, W], radii [N] int32, extra [E, H, W] or None)``:
+    the 6-tuple of the reference's call, of which it reads slots 0, 3 and 4 (gaussian_renderer/__init__.py:95) and the 4D-DRESS
+    tracking script slot 5 as well (train_mesh_lbs_4ddress.py:299).  image, alpha and extra carry a graph when an input other than
+    means2D requires grad (module docstring)."""
 
     def __init__(self, raster_settings: GaussianRasterizationSettings, private_scratch: bool = False):
         """The reference builds a new rasteriser for every frame (gaussian_renderer/__init__.py:51), so the scratch is shared
@@ -217,7 +279,7 @@ class GaussianRasterizer:
         return {k: int(getattr(st, k)) for k, _ in L.RasterStats._fields_}
 
     def forward(self, means3D, means2D=None, opacities=None, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3Ds_precomp=None):
+                cov3Ds_precomp=None, extra_attrs=None):
         s = self.raster_settings
         if (shs is None) == (colors_precomp is None):
             raise RuntimeError("Please provide exactly one of either SHs or precomputed colors!")
@@ -235,7 +297,8 @@ class GaussianRasterizer:
         given = dict(means3D=means3D, opacities=opacities, shs=shs, colors_precomp=colors_precomp, scales=scales, rotations=rotations,
                      cov3Ds_precomp=cov3Ds_precomp)
         # means2D requiring grad alone builds no graph: the eval loop passes it so and reads no gradient
-        graph = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in given.values())
+        graph = torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in given.values())
+                                             or (isinstance(extra_attrs, torch.Tensor) and extra_attrs.requires_grad))
         with torch.no_grad():
             m = expect(means3D.detach(), torch.float32, "means3D")
             if m.dim() != 2 or m.shape[1] != 3:
@@ -264,8 +327,13 @@ class GaussianRasterizer:
             campos, bg = small(s.campos, "campos", (3,)), s.bg
             if not (isinstance(bg, torch.Tensor) and bg.numel() == 3):
                 raise RuntimeError("bg: expected a tensor of 3 values")
+            extra = None
+            if extra_attrs is not None:
+                extra = expect(extra_attrs.detach() if isinstance(extra_attrs, torch.Tensor) else extra_attrs, torch.float32, "extra_attrs")
+                if extra.dim() != 2 or extra.shape[0] != n or not 1 <= extra.shape[1] <= MAX_EXTRA_ATTRS:
+                    raise RuntimeError(f"extra_attrs: expected shape ({n}, E) with 1 <= E <= {MAX_EXTRA_ATTRS}, got {tuple(extra.shape)}")
             for name, t in (("opacities", op), ("shs", shs), ("colors_precomp", colors_precomp), ("scales", scales),
-                            ("rotations", rotations), ("cov3Ds_precomp", cov3Ds_precomp), ("viewmatrix", view),
+                            ("rotations", rotations), ("cov3Ds_precomp", cov3Ds_precomp), ("extra_attrs", extra), ("viewmatrix", view),
                             ("projmatrix", proj), ("campos", campos)):
                 if t is not None and t.device != dev:
                     raise RuntimeError(f"{name}: expected a tensor on {dev}")
@@ -274,16 +342,23 @@ class GaussianRasterizer:
                                   view.data_ptr(), proj.data_ptr(), campos.data_ptr())
             hd = self._handle(dev)
             if not graph:
-                image, alpha, radii = _launch_forward(hd, cs, n, n_sh, (m, shs, colors_precomp, op, scales, rotations, cov3Ds_precomp), False)
+                # a frame with extras records where every pixel stopped (the training flavour): the extra walk ends there
+                image, alpha, radii = _launch_forward(hd, cs, n, n_sh, (m, shs, colors_precomp, op, scales, rotations, cov3Ds_precomp),
+                                                      extra is not None)
+                blended = None if extra is None else _launch_extra(hd, cs, n, extra)
                 self._last, hd.last_user = hd, weakref.ref(self)
-                return image, None, None, alpha, radii, None
+                return image, None, None, alpha, radii, blended
         # the validated values above are detached views of these: the same memory, now with the graph's leaves attached
         fr = _Frame()
         fr.cs, fr.keep, fr.hd, fr.n, fr.n_sh, fr.h, fr.w = cs, (view, proj, campos), hd, n, n_sh, h, w
         m2 = means2D if isinstance(means2D, torch.Tensor) and means2D.requires_grad else None
-        image, alpha, radii = _Rasterize.apply(fr, given["means3D"], m2, given["opacities"], given["shs"], given["colors_precomp"],
-                                               given["scales"], given["rotations"], given["cov3Ds_precomp"])
+        leaves = (fr, given["means3D"], m2, given["opacities"], given["shs"], given["colors_precomp"], given["scales"], given["rotations"],
+                  given["cov3Ds_precomp"])
+        if extra_attrs is None:
+            (image, alpha, radii), blended = _Rasterize.apply(*leaves), None
+        else:
+            image, alpha, radii, blended = _RasterizeExtra.apply(*leaves, extra_attrs)
         self._last, hd.last_user = hd, weakref.ref(self)
-        return image, None, None, alpha, radii, None
+        return image, None, None, alpha, radii, blended
 
     __call__ = forward

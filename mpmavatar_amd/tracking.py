@@ -4,6 +4,7 @@ appearance loop does not have (csrc/track.hip, csrc/track_math.hpp):
 
     fg = FaceGaussians(faces)                                                     # once per mesh
     rendervar = fg.render_vars(vertices, log_scales, logit_opacities)             # params2rendervar :209-225, one Gaussian per face
+    rendervar = fg.render_vars(..., extra_attrs=variables['cloth_mask'])          # the 4D-DRESS one, train_mesh_lbs_4ddress.py:260-277
     area, scale, opacity = fg.losses(vertices, log_scales, logit_opacities)       # losses['area'], ['scale'], ['opacity'] :242-268
     smplx_vn = VertexNormals(body_faces)(smplx_v)                                 # compute_vertex_normals, utils/geo_utils.py:8-19
     collision = collision_penalty(vertices[cloth_v_idx], smplx_v, smplx_vn)       # preprocess/losses/physics.py:6-20
@@ -159,12 +160,19 @@ class FaceGaussians(_Mesh):
             raise RuntimeError("FaceGaussians: the tensors must be on the same device")
         return v, ls, lo
 
-    def render_vars(self, vertices, log_scales, logit_opacities) -> dict:
+    def render_vars(self, vertices, log_scales, logit_opacities, extra_attrs=None) -> dict:
         """-> {means3D [F, 3], rotations [F, 4] WXYZ, scales [F, 3], opacities [F, 1]}; ``colors_precomp`` and ``means2D`` are the
-        caller's.  The quaternion conversion is UNCONFIRMED against pytorch3d (module docstring); ``q`` and ``-q`` render alike."""
+        caller's.  The quaternion conversion is UNCONFIRMED against pytorch3d (module docstring); ``q`` and ``-q`` render alike.
+        ``extra_attrs`` [F, E], the 4D-DRESS script's ``variables['cloth_mask']`` (train_mesh_lbs_4ddress.py:260-277), is handed on under
+        its key as it is, for the rasteriser's sixth slot; without it the dict has no such key."""
         v, ls, lo = self._inputs(vertices, log_scales, logit_opacities)
+        if extra_attrs is not None and (not isinstance(extra_attrs, torch.Tensor) or extra_attrs.dim() != 2 or extra_attrs.shape[0] != self.n_faces):
+            raise RuntimeError(f"extra_attrs: expected a tensor of shape ({self.n_faces}, E)")
         out = _RenderVars.apply(v, ls, lo, self) if wants_grad(v, ls, lo) else _launch_render(self, v, ls, lo)
-        return dict(zip(("means3D", "rotations", "scales", "opacities"), out))
+        rendervar = dict(zip(("means3D", "rotations", "scales", "opacities"), out))
+        if extra_attrs is not None:
+            rendervar["extra_attrs"] = extra_attrs
+        return rendervar
 
     def terms(self, vertices, log_scales, logit_opacities) -> torch.Tensor:
         """-> the [3] tensor (area, scale, opacity), for callers who weight with a tensor product"""
