@@ -11,11 +11,16 @@ without its dataset, its SMPL-X forward and pytorch3d:
                losses['collision_l'] = collision_penalty(vertices[cloth_v_idx], smplx_v, smplx_vn)   -> mpmhip_track_collision_forward
                loss.backward(); optimizer.step()                                   (FusedAdam, initialize_optimizer's groups :182-193)
 
-    python examples/tracking_step_demo.py [--steps 30] [--size 64] [--cloth-mask]
+    python examples/tracking_step_demo.py [--steps 30] [--size 64] [--cloth-mask] [--dress4d]
 
 ``--cloth-mask`` adds the 4D-DRESS script's garment term (preprocess/train_mesh_lbs_4ddress.py:260-277, :299, :306): a synthetic
 two-garment labelling of the faces (upper: face centre above the equator, lower: below) goes in as ``extra_attrs``, the rasteriser's
 sixth slot is the rendered garment mask, and ``losses['cloth_mask'] = l1_loss(cloth_mask, gt_cloth_mask)`` enters with weight 2.
+
+``--dress4d`` adds the other terms of that script's first timestep: ``losses['laplacian'] = lap.loss(vertices)`` (:363, weight 1;
+``MeshLaplacian`` stands for the dense ``laplacian_matrix`` of :212-214 -> mpmhip_track4d_laplacian_forward) and ``scale_ratio``,
+``scale_edge_ratio``, ``scale_edge_ratio_var`` = ``fg.scale_ratio_losses(vertices, rendervar['scales'])`` (:361, weights 10, 1000, 10
+-> mpmhip_track4d_scale_ratio_forward).
 
 The mesh is a 320-face icosphere of radius 0.5 with one Gaussian per face and a smaller sphere inside as the body, its vertex normals
 from ``VertexNormals``.  The ground-truth image and mask are rendered from a displaced copy of the mesh with other colours; Adam then
@@ -35,18 +40,19 @@ from mpmavatar_amd.image_loss import image_loss, l1_loss  # noqa: E402
 from mpmavatar_amd.optim import FusedAdam  # noqa: E402
 from mpmavatar_amd.rasterizer import GaussianRasterizationSettings, GaussianRasterizer, look_at_camera  # noqa: E402
 from mpmavatar_amd.regularizers import MeshRegularizer  # noqa: E402
-from mpmavatar_amd.tracking import FaceGaussians, VertexNormals, collision_penalty  # noqa: E402
+from mpmavatar_amd.tracking import FaceGaussians, MeshLaplacian, VertexNormals, collision_penalty  # noqa: E402
 
 # loss_weights of get_loss (:287-291) with the argparse defaults (:545-553)
 WEIGHTS = {"im": 1.0, "msk": 1.0, "scale": 1.0, "normal": 0.1, "opacity": 0.05, "iso": 20.0, "area": 50.0, "eq_faces_weight": 1000.0,
-           "collision_l": 10.0, "cloth_mask": 2.0}               # cloth_mask: train_mesh_lbs_4ddress.py:306, the 4D-DRESS script alone
+           "collision_l": 10.0, "cloth_mask": 2.0,               # cloth_mask: train_mesh_lbs_4ddress.py:306, the 4D-DRESS script alone
+           "laplacian": 1.0, "scale_ratio": 10.0, "scale_edge_ratio": 1000.0, "scale_edge_ratio_var": 10.0}      # :369, likewise
 LR_MEANS3D, LR_COLORS = 0.00004, 0.0025                  # --lr_means3D, --lr_colors
 
 
 class Scene:
     """Everything one tracking step needs; ``params`` are the six leaves of the reference's ``params`` dict."""
 
-    def __init__(self, size=64, device="cuda:0", seed=0, eye=(0.0, 0.3, -2.0), cloth_mask=False):
+    def __init__(self, size=64, device="cuda:0", seed=0, eye=(0.0, 0.3, -2.0), cloth_mask=False, dress4d=False):
         dev = torch.device(device)
         g = torch.Generator(device="cpu").manual_seed(seed)
         rnd = lambda *s: torch.randn(*s, generator=g)
@@ -56,6 +62,7 @@ class Scene:
         self.faces = torch.tensor(np.asarray(faces, np.int32), device=dev)
         self.fg = FaceGaussians(self.faces)
         self.reg = MeshRegularizer(self.faces, verts0)                           # neighbor_dist, neighbor_weight from the first frame
+        self.lap = MeshLaplacian(self.faces) if dress4d else None                # in place of variables['laplacian_matrix']
         self.smplx_v = torch.tensor(np.asarray(body_v, np.float32), device=dev)
         self.smplx_vn = VertexNormals(torch.tensor(np.asarray(body_f, np.int32), device=dev))(self.smplx_v)
         self.cloth_v_idx = torch.arange(verts0.shape[0], device=dev)
@@ -87,9 +94,11 @@ class Scene:
         self.losses = {}
 
     def render(self, curr_id=0):
-        """-> (im [3, size, size] behind the camera affine, msk [1, size, size], radius [F], cloth_mask [2, size, size] or None)"""
+        """-> (im [3, size, size] behind the camera affine, msk [1, size, size], radius [F], cloth_mask [2, size, size] or None); the
+        Gaussians' scales stay in ``self.scales`` for the scale-ratio terms"""
         p = self.params
         rendervar = self.fg.render_vars(p["vertices"], p["log_scales"], p["logit_opacities"], extra_attrs=self.cloth_table)
+        self.scales = rendervar["scales"]
         rendervar["colors_precomp"] = p["rgb_colors"]
         rendervar["means2D"] = torch.zeros_like(rendervar["means3D"], requires_grad=True)
         im, _, _, msk, radius, cloth_mask = GaussianRasterizer(raster_settings=self.cam)(**rendervar)
@@ -105,6 +114,9 @@ class Scene:
         losses["area"], losses["scale"], losses["opacity"] = self.fg.losses(p["vertices"], p["log_scales"], p["logit_opacities"])
         losses["normal"], losses["iso"], losses["eq_faces_weight"] = self.reg(p["vertices"])
         losses["collision_l"] = collision_penalty(p["vertices"][self.cloth_v_idx], self.smplx_v, self.smplx_vn, return_average=True)
+        if self.lap is not None:                                                 # :361 (the initial timestep) and :363
+            losses["scale_ratio"], losses["scale_edge_ratio"], losses["scale_edge_ratio_var"] = self.fg.scale_ratio_losses(p["vertices"], self.scales)
+            losses["laplacian"] = self.lap.loss(p["vertices"])
         self.losses = {k: float(v.detach()) for k, v in losses.items()}
         return sum(WEIGHTS[k] * v for k, v in losses.items()), radius
 
@@ -114,8 +126,9 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--size", type=int, default=64)
     ap.add_argument("--cloth-mask", action="store_true")
+    ap.add_argument("--dress4d", action="store_true")
     a = ap.parse_args(argv)
-    sc = Scene(a.size, cloth_mask=a.cloth_mask)
+    sc = Scene(a.size, cloth_mask=a.cloth_mask, dress4d=a.dress4d)
     opt = FusedAdam([{"params": [v], "name": k, "lr": sc.lrs[k]} for k, v in sc.params.items()], lr=0.0, eps=1e-15)
     losses = []
     for step in range(a.steps + 1):

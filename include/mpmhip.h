@@ -942,6 +942,48 @@ int mpmhip_track_collision_forward(int32_t device, void *stream, const float *va
 int mpmhip_track_collision_backward(int32_t device, void *stream, int32_t n, const float *nb, int32_t n_body, const int32_t *index,
                                     const float *distance, float eps, int32_t mode, const float *g, float *d_va);
 
+/* ---- the 4D-DRESS tracking script's two further terms (preprocess/train_mesh_lbs_4ddress.py:279-292, :361, :363) ---------------------
+ * Stateless like the entry points above, and under the same rules: fp32 data, sums in fp64 in a fixed order, no floating-point
+ * atomics, workgroups of MPMHIP_TRACK_TPB.  MPMHIP_ERR_INVALID, nothing launched: a count that is not positive, a required pointer
+ * NULL, a scratch shorter than its macro says.
+ *
+ * mpmhip_track4d_laplacian_forward replaces variables['laplacian_matrix'].mm(vertices).norm(dim=1).mean() (:363) and the dense
+ * [V, V] matrix of :212-214 (Meshes(...).laplacian_packed().to_dense()) by a gather over the vertex adjacency: nbr_start
+ * [n_verts+1] / nbr [n_nbr] is the CSR table of the undirected edges in both directions, ascending within a row.
+ *   out_lv [n_verts*3]   (Lv)_i = (sum_{j in N(i)} v_j) / deg(i) - v_i; -v_i for a vertex with no neighbour
+ *   out_value [1]        mean_i |(Lv)_i| over all n_verts rows
+ * The sum is divided by the degree (pytorch3d stores 1 / deg in the matrix: a difference at rounding level), so neighbours that sum
+ * to exactly deg * v_i give exactly 0.  The uniform Laplacian restates pytorch3d's and is UNCONFIRMED against pytorch3d itself.
+ * Either output may be NULL; scratch [n_scratch >= MPMHIP_TRACK4D_LAPLACIAN_SCRATCH(n_verts)] doubles is needed with out_value. */
+#define MPMHIP_TRACK4D_LAPLACIAN_SCRATCH(n_verts) (((int64_t)(n_verts) + MPMHIP_TRACK_TPB - 1) / MPMHIP_TRACK_TPB)
+int mpmhip_track4d_laplacian_forward(int32_t device, void *stream, const float *verts, int32_t n_verts, const int32_t *nbr_start,
+                                     const int32_t *nbr, int32_t n_nbr, double *scratch, int32_t n_scratch, float *out_lv, float *out_value);
+/* d_verts [n_verts*3] of :363 from the forward's lv and the upstream scalar g [1] on the device:
+ * u_i = (g / n_verts) lv_i / |lv_i| (0 where the norm is 0, torch's subgradient), d_verts_j = sum_{i in N(j)} u_i / deg(i) - u_j.
+ * A gather over the same table; the vertices are not read.  d_verts == NULL: nothing launched. */
+int mpmhip_track4d_laplacian_backward(int32_t device, void *stream, const float *lv, int32_t n_verts, const int32_t *nbr_start,
+                                      const int32_t *nbr, int32_t n_nbr, const float *g, float *d_verts);
+/* scale_ratio_loss (:279-292, called at :361 with the thresholds 5.0 and 1.0) on scales [n_faces*3], the `scales` entry of the
+ * render variables.  Per face m = the longest of |v_k - v_{(k+1) mod 3}|, a = max(s0, s1), b = min(s0, s1), r = a / (b + 1e-8),
+ * q = a / (m + 1e-8):
+ *   out_terms[0] scale_ratio          = mean(max(r, th_ratio) - th_ratio)
+ *   out_terms[1] scale_edge_ratio     = mean(max(q, th_edge) - th_edge)
+ *   out_terms[2] scale_edge_ratio_var = the unbiased variance of q (NaN for n_faces == 1, as torch.var)
+ *   out_terms[3] the mean of q, which the backward reads
+ * scratch [n_scratch >= MPMHIP_TRACK4D_SCALE_RATIO_SCRATCH(n_faces)] doubles. */
+#define MPMHIP_TRACK4D_SCALE_RATIO_SCRATCH(n_faces) (4 * (((int64_t)(n_faces) + MPMHIP_TRACK_TPB - 1) / MPMHIP_TRACK_TPB))
+int mpmhip_track4d_scale_ratio_forward(int32_t device, void *stream, const float *verts, int32_t n_verts, const int32_t *faces, int32_t n_faces,
+                                       const float *scales, float th_ratio, float th_edge, double *scratch, int32_t n_scratch,
+                                       float *out_terms);
+/* from terms (the forward's four) and g_terms [3] on the device to d_verts [n_verts*3] and d_scales [n_faces*3] (column 2 exactly 0),
+ * each written in full, NULL = not wanted.  Decisions as torch takes them on the CPU: the first of equal maxima and of equal minima,
+ * slope 1 at r == th_ratio and q == th_edge, no gradient through a longest edge of length zero.  A g_terms entry that is exactly zero
+ * leaves no trace.  d_stencil [n_faces*9] and the vertex -> corner table (above) are needed only with d_verts. */
+int mpmhip_track4d_scale_ratio_backward(int32_t device, void *stream, const float *verts, int32_t n_verts, const int32_t *faces,
+                                        int32_t n_faces, const float *scales, float th_ratio, float th_edge, const float *terms,
+                                        const float *g_terms, const int32_t *vert_start, const int32_t *vert_items, float *d_stencil,
+                                        float *d_verts, float *d_scales);
+
 /* ---- re-posing: k nearest neighbours and linear-blend skinning (utils/smplx_deformer.py:164-337) ------------------------------------
  * What the reference's drivers do with SmplxDeformer between a tracked mesh and the solver's input (train_material_params.py:335-349,
  * preprocess/train_mesh_lbs_actorshq.py:495-516), without pytorch3d or open3d.  Stand-alone maps on [dev] arrays; nothing allocates

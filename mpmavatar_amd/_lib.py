@@ -175,6 +175,10 @@ SIGNATURES = {
     "mpmhip_track_vertex_normals": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp]),
     "mpmhip_track_collision_forward": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_float, C.c_int32] + [vp] * 5),
     "mpmhip_track_collision_backward": (C.c_int, [C.c_int32, vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_float, C.c_int32, vp, vp]),
+    "mpmhip_track4d_laplacian_forward": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp]),
+    "mpmhip_track4d_laplacian_backward": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp]),
+    "mpmhip_track4d_scale_ratio_forward": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_float, C.c_float, vp, C.c_int32, vp]),
+    "mpmhip_track4d_scale_ratio_backward": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_float, C.c_float] + [vp] * 7),
     "mpmhip_knn_scratch": (C.c_int, [C.c_int32] * 5 + [C.POINTER(C.c_int64)]),
     "mpmhip_knn": (C.c_int, [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64, vp, vp]),
     "mpmhip_shepard_weights": (C.c_int, [C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp]),

@@ -17,8 +17,8 @@ LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(LIBDIR, "obj")
 LIB = os.path.join(LIBDIR, "libmpmhip.so")
 FAST_SOURCES = ["fast.hip", "resort.hip", "p2g.hip", "g2p.hip", "dist.hip"]   # the fast back end (one translation unit until round 4)
-SOURCES = ["api.hip", "common.hip", "baseline.hip"] + FAST_SOURCES + ["frames.hip", "frames_backward.hip", "geo.hip", "raster.hip", "raster_backward.hip", "raster_extra.hip", "image_loss.hip", "shade.hip", "shadow.hip", "reg.hip", "ao.hip", "densify.hip", "adam.hip", "lpips.hip", "track.hip", "repose.hip", "image_head.hip"]
-HEADERS = ["ctx.hpp", "mpm_math.hpp", "geo_math.hpp", "frames_math.hpp", "frames_grad_math.hpp", "raster_math.hpp", "raster_grad_math.hpp", "raster_extra_math.hpp", "shade_math.hpp", "shadow_math.hpp", "reg_math.hpp", "ao_math.hpp", "densify_math.hpp", "adam_math.hpp", "lpips_math.hpp", "raster_state.hpp", "entry.hpp", "image_loss_math.hpp", "image_head_math.hpp", "track_math.hpp", "nn_device.hpp", "repose_math.hpp", "knn_device.hpp", "block_sum.hpp", "bc.hpp", "launch_layout.hpp", "halo_tables.hpp", "fast_device.hpp", "p2g_device.hpp", "splat_device.hpp", "g2p_device.hpp", "fast_state.hpp", os.path.join("..", "..", "include", "mpmhip.h")]
+SOURCES = ["api.hip", "common.hip", "baseline.hip"] + FAST_SOURCES + ["frames.hip", "frames_backward.hip", "geo.hip", "raster.hip", "raster_backward.hip", "raster_extra.hip", "image_loss.hip", "shade.hip", "shadow.hip", "reg.hip", "ao.hip", "densify.hip", "adam.hip", "lpips.hip", "track.hip", "track4d.hip", "repose.hip", "image_head.hip"]
+HEADERS = ["ctx.hpp", "mpm_math.hpp", "geo_math.hpp", "frames_math.hpp", "frames_grad_math.hpp", "raster_math.hpp", "raster_grad_math.hpp", "raster_extra_math.hpp", "shade_math.hpp", "shadow_math.hpp", "reg_math.hpp", "ao_math.hpp", "densify_math.hpp", "adam_math.hpp", "lpips_math.hpp", "raster_state.hpp", "entry.hpp", "image_loss_math.hpp", "image_head_math.hpp", "track_math.hpp", "track4d_math.hpp", "nn_device.hpp", "repose_math.hpp", "knn_device.hpp", "block_sum.hpp", "bc.hpp", "launch_layout.hpp", "halo_tables.hpp", "fast_device.hpp", "p2g_device.hpp", "splat_device.hpp", "g2p_device.hpp", "fast_state.hpp", os.path.join("..", "..", "include", "mpmhip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-ffp-contract=fast-honor-pragmas",
          "-Wall", "-Wno-unused-function"]

@@ -1,6 +1,6 @@
 """The mesh tracking step on the device (preprocess/train_mesh_lbs_actorshq.py and train_mesh_lbs_4ddress.py): what one iteration of
 the reference's tracking loop computes between the trained ``vertices`` and the rasteriser's argument list, and the loss terms the
-appearance loop does not have (csrc/track.hip, csrc/track_math.hpp):
+appearance loop does not have (csrc/track.hip, csrc/track_math.hpp; csrc/track4d.hip, csrc/track4d_math.hpp):
 
     fg = FaceGaussians(faces)                                                     # once per mesh
     rendervar = fg.render_vars(vertices, log_scales, logit_opacities)             # params2rendervar :209-225, one Gaussian per face
@@ -8,6 +8,9 @@ appearance loop does not have (csrc/track.hip, csrc/track_math.hpp):
     area, scale, opacity = fg.losses(vertices, log_scales, logit_opacities)       # losses['area'], ['scale'], ['opacity'] :242-268
     smplx_vn = VertexNormals(body_faces)(smplx_v)                                 # compute_vertex_normals, utils/geo_utils.py:8-19
     collision = collision_penalty(vertices[cloth_v_idx], smplx_v, smplx_vn)       # preprocess/losses/physics.py:6-20
+    lap = MeshLaplacian(faces)                                                    # once per mesh, for laplacian_matrix of 4ddress :212-214
+    laplacian = lap.loss(vertices)                                                # losses['laplacian'], train_mesh_lbs_4ddress.py:363
+    ratio, edge_ratio, edge_ratio_var = fg.scale_ratio_losses(vertices, rendervar['scales'])    # scale_ratio_loss :279-292, :361
 
 The rest of the iteration is already here: ``rasterizer.GaussianRasterizer``, ``image_loss`` and ``l1_loss``, ``MeshRegularizer``
 (normal, iso, eq_faces_weight) and ``FusedAdam``.  INTEGRATION.md, "Before the solver: the tracking step", has the switch-over.
@@ -183,6 +186,17 @@ class FaceGaussians(_Mesh):
         """-> (area, scale, opacity): 0-dim fp32 tensors"""
         return self.terms(vertices, log_scales, logit_opacities).unbind(0)
 
+    def scale_ratio_losses(self, vertices, scales, scale_ratio_th=5.0, scale_edge_ratio_th=1.0):
+        """``scale_ratio_loss`` (below) over this mesh's cached face table -> (scale_ratio, scale_edge_ratio, scale_edge_ratio_var),
+        0-dim fp32.  ``scales`` [F, 3] is the ``scales`` entry of ``render_vars``: through its graph the gradient reaches ``log_scales``."""
+        v = self._verts(vertices, "verts")
+        s = expect(scales, torch.float32, "scale", shape=(self.n_faces, 3))
+        if s.device != v.device:
+            raise RuntimeError("scale and verts must be on the same device")
+        th = (float(scale_ratio_th), float(scale_edge_ratio_th))
+        terms = _ScaleRatio.apply(v, s, self, th) if wants_grad(v, s) else _launch_scale_ratio(self, v, s, th)[:3]
+        return terms.unbind(0)
+
     def _geometry(self, vertices, normals, areas):
         v = self._verts(vertices).detach()
         call("mpmhip_track_face_geometry", v.device, v.data_ptr(), v.shape[0], self.faces.data_ptr(), self.n_faces, ptr(normals), ptr(areas))
@@ -307,3 +321,139 @@ def nearest_neighbour(A, B) -> torch.Tensor:
     A [n, 3] (the lowest index on an exact tie)."""
     a, b, _ = _points(A.detach() if isinstance(A, torch.Tensor) else A, B.detach() if isinstance(B, torch.Tensor) else B)
     return _launch_collision(a, b, None, 0.0, _MODES["distance"])[0]
+
+
+# ---- the 4D-DRESS script's two further terms (train_mesh_lbs_4ddress.py:279-292, :361, :363; csrc/track4d.hip) -------------------------
+
+def _launch_laplacian(lap, v, want_lv, want_value):
+    """-> (Lv [V, 3] or None, value [1] or None)"""
+    dev, n_v = v.device, v.shape[0]
+    start, nbr = lap._adjacency(n_v)
+    lv = _empty(dev, n_v, 3) if want_lv else None
+    value = _empty(dev, 1) if want_value else None
+    n_scratch = (n_v + _TPB - 1) // _TPB
+    scratch = torch.empty(n_scratch, dtype=torch.float64, device=dev) if want_value else None
+    call("mpmhip_track4d_laplacian_forward", dev, v.data_ptr(), n_v, start.data_ptr(), nbr.data_ptr(), nbr.shape[0], ptr(scratch), n_scratch,
+         ptr(lv), ptr(value))
+    return lv, value
+
+
+class _Laplacian(torch.autograd.Function):
+    """vertices -> mean_i |(Lv)_i|; the backward reads the saved Lv and the table, not the vertices"""
+
+    @staticmethod
+    def forward(ctx, v, lap):
+        lv, value = _launch_laplacian(lap, v, True, True)
+        ctx.lap = lap
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(lv)
+        return value.reshape(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_value):
+        lv, = ctx.saved_tensors
+        g = upstream(g_value, (1,))
+        if g is None:
+            return None, None
+        n_v = lv.shape[0]
+        start, nbr = ctx.lap._adjacency(n_v)
+        d_v = torch.empty_like(lv)
+        call("mpmhip_track4d_laplacian_backward", lv.device, lv.data_ptr(), n_v, start.data_ptr(), nbr.data_ptr(), nbr.shape[0], g.data_ptr(),
+             d_v.data_ptr())
+        return d_v, None
+
+
+class MeshLaplacian(_Mesh):
+    """``losses['laplacian']`` of train_mesh_lbs_4ddress.py:363 without the dense [V, V] ``laplacian_matrix`` of :212-214: the uniform
+    Laplacian as a gather over the vertex adjacency.  With E the undirected edges of ``faces`` (each once, however many faces share
+    it), N(i) the neighbours of i and deg(i) their number:
+
+        (Lv)_i = (sum_{j in N(i)} v_j) / deg(i) - v_i        -v_i for a vertex in no face
+        loss   = mean_i |(Lv)_i|                             over all V rows of ``vertices``
+
+    The sum runs in ascending j and is divided by the degree, so neighbours that sum to exactly deg * v_i give exactly zero;
+    pytorch3d stores 1 / deg in the matrix, a difference at rounding level.  Where |(Lv)_i| is zero the gradient through it is zero,
+    as torch's ``norm``.  UNCONFIRMED against pytorch3d's ``laplacian_packed`` itself (not installed where the fixtures are made).
+    A face that names one vertex twice raises: pytorch3d would put a self-edge into the matrix.  The adjacency (CSR, ascending within
+    a row) is built with torch ops once per vertex count, at first use."""
+
+    def __init__(self, faces: torch.Tensor):
+        super().__init__(faces)
+        f = self.faces
+        if bool(((f[:, 0] == f[:, 1]) | (f[:, 1] == f[:, 2]) | (f[:, 2] == f[:, 0])).any()):
+            raise RuntimeError("faces: a face names one vertex twice")
+        self._adj_key = self._adj_value = None
+
+    def _adjacency(self, n_verts):
+        if self._adj_key != n_verts:
+            f = self.faces.long()
+            e = torch.cat([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
+            e = torch.cat([e, e.flip(1)])                                        # both directions
+            key = torch.unique(e[:, 0] * n_verts + e[:, 1])                      # sorted: by row, ascending within it; an edge counts once
+            row = torch.div(key, n_verts, rounding_mode="floor")
+            start = torch.zeros(n_verts + 1, dtype=torch.int32, device=f.device)
+            start[1:] = torch.cumsum(torch.bincount(row, minlength=n_verts), 0)
+            self._adj_key, self._adj_value = n_verts, (start, (key - row * n_verts).to(torch.int32))
+        return self._adj_value
+
+    def loss(self, vertices) -> torch.Tensor:
+        """-> the 0-dim fp32 ``variables['laplacian_matrix'].mm(vertices).norm(dim=1).mean()``, with gradient to ``vertices``"""
+        v = self._verts(vertices)
+        return _Laplacian.apply(v, self) if wants_grad(v) else _launch_laplacian(self, v, False, True)[1].reshape(())
+
+    def apply(self, vertices) -> torch.Tensor:
+        """-> Lv [V, 3]; forward only"""
+        return _launch_laplacian(self, self._verts(vertices).detach(), True, False)[0]
+
+
+def _launch_scale_ratio(fg, v, s, th):
+    dev = v.device
+    terms = _empty(dev, 4)
+    n_scratch = 4 * ((fg.n_faces + _TPB - 1) // _TPB)
+    scratch = torch.empty(n_scratch, dtype=torch.float64, device=dev)
+    call("mpmhip_track4d_scale_ratio_forward", dev, v.data_ptr(), v.shape[0], fg.faces.data_ptr(), fg.n_faces, s.data_ptr(), th[0], th[1],
+         scratch.data_ptr(), n_scratch, terms.data_ptr())
+    return terms
+
+
+class _ScaleRatio(torch.autograd.Function):
+    """(vertices, scales) -> [scale_ratio, scale_edge_ratio, scale_edge_ratio_var]"""
+
+    @staticmethod
+    def forward(ctx, v, s, fg, th):
+        terms = _launch_scale_ratio(fg, v, s, th)
+        ctx.fg, ctx.th = fg, th
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(v, s, terms)
+        return terms[:3].clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_terms):
+        v, s, terms = ctx.saved_tensors
+        fg = ctx.fg
+        g = upstream(g_terms)
+        if g is None:
+            return None, None, None, None
+        d_v, d_s = [torch.empty_like(t) if want else None for want, t in zip(ctx.needs_input_grad[:2], (v, s))]
+        start, items, stencil = None, None, None
+        if d_v is not None:
+            start, items = fg._table(v.shape[0])
+            stencil = _empty(v.device, fg.n_faces, 3, 3)
+        call("mpmhip_track4d_scale_ratio_backward", v.device, v.data_ptr(), v.shape[0], fg.faces.data_ptr(), fg.n_faces, s.data_ptr(),
+             ctx.th[0], ctx.th[1], terms.data_ptr(), g.data_ptr(), ptr(start), ptr(items), ptr(stencil), ptr(d_v), ptr(d_s))
+        return d_v, d_s, None, None
+
+
+def scale_ratio_loss(verts, faces, scale, scale_ratio_th=5.0, scale_edge_ratio_th=1.0):
+    """``scale_ratio_loss`` of train_mesh_lbs_4ddress.py:279-292 (name, argument order and defaults): per face, with m the longest
+    edge, a = max(s0, s1), b = min(s0, s1), r = a / (b + 1e-8), q = a / (m + 1e-8),
+
+        scale_ratio = mean(max(r, th_r) - th_r)    scale_edge_ratio = mean(max(q, th_e) - th_e)    scale_edge_ratio_var = var(q)
+
+    (unbiased; NaN for a single face, as in the reference).  Gradients go to ``verts`` through m and to ``scale[:, :2]`` (column 2
+    gets exact zeros); the decisions are held fixed as torch takes them on the CPU: the first of equal maxima and minima, clamp's
+    slope 1 at x == th, no gradient through a longest edge of length zero.  Checks ``faces`` and builds the vertex -> corner table on
+    every call; ``FaceGaussians.scale_ratio_losses`` keeps both."""
+    return FaceGaussians(faces).scale_ratio_losses(verts, scale, scale_ratio_th, scale_edge_ratio_th)
